@@ -14,7 +14,13 @@ Multi-GPU (python -m torch.distributed.run --nproc-per-node N bench.py
 shard of signatures (no data-path collective -- nothing is reduced);
 RCCL only carries the timing barrier and the max-over-ranks.
 
-Extra measurements on rank 0 at N=1:
+A plain run sets up, warms up, times --steps steps, writes its outputs
+(--dump-outputs DIR: DIR/codes.npy, the per-signature codes of the last
+timed step as float32; codes_rank<r>.npy per rank at N > 1) and prints the
+result line.  Everything below runs only with --full (--no-cpu and
+--no-latency trim the full run and imply it).
+
+Extra measurements on rank 0 at N=1 (--full):
   roofline     per-kernel HIP-event durations over the timed launches,
                algorithmic int32 ops / duration
   latency      C2 at its own granularity: 4096-signature batches of a
@@ -131,8 +137,14 @@ def parse():
     ap.add_argument("--unique", type=int, default=0,
                     help="distinct signatures per GPU (0: one per signature of a step, so the timed launches "
                          "never re-read an input that could sit in the 256 MB MALL)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-latency", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel roofline, the C2 ring latency legs, the "
+                         "streamed C2 leg and the CPU baseline, and check every code against the reference build")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the codes of the last timed step to DIR/codes.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline leg (implies --full)")
+    ap.add_argument("--no-latency", action="store_true",
+                    help="--full without the ring latency and streamed legs (implies --full)")
     ap.add_argument("--latency-batches", type=int, default=10000, help="C2 latency: >= 10^4 batches (SURVEY 8d)")
     ap.add_argument("--ring-depth", type=int, default=8, help="ring slots of the C2 streaming leg")
     ap.add_argument("--ring-window", type=int, default=6,
@@ -143,7 +155,12 @@ def parse():
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     ap.add_argument("--stream-batches", type=int, default=48,
                     help="batches of the PCIe-inclusive large-batch C2 leg (c2_streamed)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    # the two options trim the full run, so asking for either selects it
+    a.full = a.full or a.no_cpu or a.no_latency
+    if a.dry_cpu and a.dump_outputs:
+        ap.error("--dump-outputs: a --dry-cpu rehearsal verifies nothing, there are no codes to write")
+    return a
 
 
 def usable_cores():
@@ -287,6 +304,29 @@ def valid_corpus_ok(hist, n):
     return set(hist) <= {"0", "-3"} and rej <= max(4, int(n * 1e-5))
 
 
+DUMP_MAX_BYTES = 64 << 20
+# what the caller's code buffer holds when the timed region starts (no
+# verify code has this value): an entry of the dump that still reads so was
+# written by none of the timed steps
+CODE_UNWRITTEN = 127
+
+
+def dump_outputs(d, name, codes):
+    """The codes the timed path left in the caller's buffer, as d/<name>.npy
+    in float32 (a code is a small integer: exact).  The buffer is set to
+    CODE_UNWRITTEN before the first timed step, not before each: the steps
+    are the same launch, and a code left by an earlier timed step cannot be
+    told from the last step's.  The corpus is all valid, so nearly every
+    entry is 0 and two builds are compared on accept / reject codes, one per
+    signature, nothing finer.  Past DUMP_MAX_BYTES a
+    fixed, seeded sample of the signatures, in index order."""
+    os.makedirs(d, exist_ok=True)
+    keep = DUMP_MAX_BYTES // 4
+    if len(codes) > keep:
+        codes = codes[np.sort(np.random.default_rng(0).choice(len(codes), keep, replace=False))]
+    np.save(os.path.join(d, name + ".npy"), codes.astype(np.float32))
+
+
 def all_ranks_ok(ok, dist, red_dev):
     if not dist:
         return ok
@@ -405,17 +445,23 @@ def main():
     torch.cuda.synchronize()
     hist = codes_hist(d_out.cpu().numpy())
     ok = valid_corpus_ok(hist, n_step)
-    solo = rank == 0 and world == 1
+    solo = a.full and rank == 0 and world == 1
     def on_start():
-        eng.dev_stats_begin()
-        eng.dsm_clock(clear=True)
+        # before the clock starts: every code the run reports or dumps was written by a timed step
+        d_out.fill_(CODE_UNWRITTEN)
+        torch.cuda.synchronize()
+        if solo:
+            eng.dev_stats_begin()
+            eng.dsm_clock(clear=True)
     elapsed = timed_region(step, a.steps, max(a.warmup - 1, 0), dist, red_dev, torch.cuda.synchronize,
-                           on_start=on_start if solo else None)
+                           on_start=on_start)
     live = eng.dev_stats_end() if solo else None
     clock = eng.dsm_clock() if solo else None
     ok = all_ranks_ok(ok, dist, red_dev)
     res = result_line(a, world, n_step, elapsed, ok, base, hist)
     value = res["value"]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, "codes" if world == 1 else f"codes_rank{rank}", d_out.cpu().numpy())
 
     if solo:
         # per-kernel durations LIVE over the timed launches: HIP events around

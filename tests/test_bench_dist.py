@@ -46,6 +46,39 @@ def test_bench_single_rank_dry():
     assert res["n_gpus"] == 1 and res["value"] > 0
 
 
+def test_dump_outputs_float32_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: the codes as float32, exact; past the size bound the
+    same seeded sample of the signatures on every run, in index order"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    codes = np.array([0, -1, -2, -3] * 250, np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), "codes", codes)
+    got = np.load(tmp_path / "a" / "codes.npy")
+    assert got.dtype == np.float32 and (got == codes).all()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 400)
+    idx = np.arange(1000, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "b"), "codes", idx)
+    bench.dump_outputs(str(tmp_path / "c"), "codes", idx)
+    b, c = np.load(tmp_path / "b" / "codes.npy"), np.load(tmp_path / "c" / "codes.npy")
+    assert b.nbytes == 400 and (b == c).all() and (np.diff(b) > 0).all()
+
+
+def test_dump_outputs_refused_on_dry_cpu(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-cpu", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not (tmp_path / "d").exists()
+
+
+def test_full_is_off_by_default_and_implied_by_its_trims(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    for argv, full in (([], False), (["--full"], True), (["--no-cpu"], True), (["--no-latency"], True),
+                       (["--gpus", "1", "--steps", "5", "--warmup", "2"], False)):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        assert bench.parse().full is full, argv
+
+
 def test_traffic_summary_held_to_the_kernels_build(tmp_path):
     """roofline.traffic only from a PMC summary of the loaded device code
     (fd_ed25519_gpu_kernels_id) at this launch size; the committed summary

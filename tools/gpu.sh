@@ -72,7 +72,7 @@ for step in "$@"; do
       pmc "quad_${tag}" "$R/$lib" $P1 -- "$R/tools/pmc_ring.py" quad 4096 || exit 1 ;;
     pmcthr)
       mkdir -p gpurun_out/pmc
-      B=("$R/bench.py" --steps 3 --warmup 1 --no-cpu --no-latency)
+      B=("$R/bench.py" --full --steps 3 --warmup 1 --no-cpu --no-latency)
       lib=$R/firedancer_amd/libfd_ed25519_gpu.so
       python3 -c "import firedancer_amd as fa; print(fa.kernels_id())" > gpurun_out/pmc/kernels.id || exit 1
       pmc thr_p1 "$lib" $P1 -- "${B[@]}" || exit 1
@@ -81,11 +81,11 @@ for step in "$@"; do
     pmcfetch)
       mkdir -p gpurun_out/pmc
       tag=$(basename "$arg" .so)
-      pmc "fetch_${tag}" "$R/$arg" FETCH_SIZE -- "$R/bench.py" --steps 3 --warmup 1 --no-cpu --no-latency || exit 1 ;;
+      pmc "fetch_${tag}" "$R/$arg" FETCH_SIZE -- "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu --no-latency || exit 1 ;;
     pmcsq)
       mkdir -p gpurun_out/pmc
       tag=$(basename "$arg" .so)
-      pmc "sq_${tag}" "$R/$arg" $P1 -- "$R/bench.py" --steps 3 --warmup 1 --no-cpu --no-latency || exit 1 ;;
+      pmc "sq_${tag}" "$R/$arg" $P1 -- "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu --no-latency || exit 1 ;;
     ringpaced)
       timeout -k 10 600 python3 -u tools/ring_paced.py ${arg//,/ } >> gpurun_out/ring_paced.jsonl 2> gpurun_out/ring_paced.err \
         || { echo RINGPACED FAILED; tail -20 gpurun_out/ring_paced.err; exit 1; }
