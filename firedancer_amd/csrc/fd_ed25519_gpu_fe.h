@@ -397,6 +397,28 @@ FD_DEV void fd_fe_mul( fd_gpu_fe_t & h, fd_gpu_fe_t const & f, fd_gpu_fe_t const
   fd_fe_mul_pre( h, f, f2, g, g19 );
 }
 
+/* h = f*one, limb-identical to fd_fe_mul( h, f, one ) for any int32 limbs
+   of f.  With g = [1, 0, ..., 0] the only nonzero product of column K is
+   term I = K, where the f operand is f[K] itself (the 2f pre-scale applies
+   to odd x odd pairs only, and g's limb 0 is even) sign-extended as every
+   v_mad_i64_i32 operand is, times g[0] = 1; the wrap terms are f * 19 g[j]
+   = f * 0.  So column K's sum is its seed plus (int64)f[K], and the
+   absorbed carry chain and the limb recovery run on the same integers as
+   the multiply's: the reference's AVX MUL gets these lanes for free next
+   to a lane that does multiply (the cached form's [1, 1, 1, 2d],
+   avx/fd_ed25519_ge.c:423-481); here they cost the carries alone
+   (tests/test_fe_mul_one_host.py). */
+struct fd_one_cols {
+  int32_t const * f;
+  template<int K> static constexpr int len() { return 1; }
+  template<int K, int I> FD_DEVM int64_t term( int64_t acc ) const { return acc + (int64_t)f[K]; }
+  template<int K> FD_DEVM int64_t col( int64_t acc ) const { return term<K,0>( acc ); }
+};
+FD_DEV void fd_fe_mul_one( fd_gpu_fe_t & h, fd_gpu_fe_t const & f ) {
+  fd_one_cols c = { f.v };
+  fd_fe_chain( h, c );
+}
+
 /* the product's limbs as fd_fe_limbs_t<FD_FE_RAW> leaves them */
 FD_DEV void fd_fe_mul_raw( fd_gpu_fe_t & h, fd_gpu_fe_t const & f, fd_gpu_fe_t const & g ) {
   int32_t f2[10], g19[10];

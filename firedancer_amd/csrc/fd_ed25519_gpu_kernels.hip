@@ -13,7 +13,7 @@
                     early-success quirk Q1), k = SHA-512(R||A||M) mod L,
                     signed sliding-window recodings of k and S.
      fd_k_decomp    one lane per POINT (2 per signature): lax
-                    decompression (Q3) and the [8]P small-order test,
+                    decompression (Q3) and the small-order test,
                     the uniform ~265-squaring part of the path.
      fd_k_dsm       one lane per signature: [k](-A) + [S]B with the
                     reference's 4-lane AVX operation sequence reproduced
@@ -21,6 +21,7 @@
                     (Q2) and the error-code precedence (Q4). */
 
 #include "fd_ed25519_gpu_fe.h"
+#include "fd_ed25519_gpu_smallorder.h"
 #include "fd_ed25519_gpu_sha512.h"
 #include "fd_ed25519_gpu_private.h"
 
@@ -79,6 +80,16 @@ FD_DEV void v_mul( fe4 & h, fe4 const & f, fe4 const & g ) {
   fe4 t;
 #pragma unroll
   for( int l=0; l<4; l++ ) fd_fe_mul( t.l[l], f.l[l], g.l[l] );
+  h = t;
+}
+/* MUL by the cached form's [1, 1, 1, 2d] (avx/fd_ed25519_ge.c:423-481):
+   lanes 0-2 are products by the constant one (fd_fe_mul_one: the carry
+   chain alone, same limbs), lane 3 the real multiply */
+FD_DEV void v_mul_d111( fe4 & h, fe4 const & f ) {
+  fe4 t;
+#pragma unroll
+  for( int l=0; l<3; l++ ) fd_fe_mul_one( t.l[l], f.l[l] );
+  fd_fe_mul( t.l[3], f.l[3], FD_GPU_D2 );
   h = t;
 }
 FD_DEV void v_mul3( fe4 & h, fe4 const & f, fe4 const & g ) { /* lane 3 unused by consumer */
@@ -402,34 +413,12 @@ FD_DEV void fd_pow22523( fe & out, fe const & f ) {
   fd_fe_mul( out, t0, f );
 }
 
-/* one lane of fd_ed25519_ge_p2_dbl (avx/fd_ed25519_ge.c:127-141) + the
-   p1p1 -> p2 / p3 conversions, for the [8]P test (fd_ed25519_ge.c:21-66) */
-FD_DEV void fd_small_dbl( fe (&r)[4], fe const & X, fe const & Y, fe const & Z ) {
-  fe xy, t0;
-  fd_fe_add( xy, X, Y );
-  fd_fe_sqn( r[0], X, 1 );
-  fd_fe_sqn( r[2], Y, 1 );
-  fd_fe_sqn( r[3], Z, 2 );
-  fd_fe_sqn( t0, xy, 1 );
-  fd_fe_add( r[1], r[2], r[0] );
-  fd_fe_sub( r[2], r[2], r[0] );
-  fd_fe_sub( r[0], t0, r[1] );
-  fd_fe_sub( r[3], r[3], r[2] );
-}
-
 /* field-value equality (canonical forms), the strict mode's compare */
 FD_DEV int fd_fe_value_eq( fe const & a, fe const & b ) {
   int32_t ca[10], cb[10]; fd_fe_canon( ca, a ); fd_fe_canon( cb, b );
   int eq = 1;
 #pragma unroll
   for( int i=0; i<10; i++ ) eq &= (ca[i] == cb[i]);
-  return eq;
-}
-
-FD_DEV int fd_limbs_eq( fe const & a, fe const & b ) {
-  int eq = 1;
-#pragma unroll
-  for( int i=0; i<10; i++ ) eq &= (a.v[i] == b.v[i]);
   return eq;
 }
 
@@ -499,22 +488,10 @@ fd_decomp_body( uint64_t j, uint64_t n, uint8_t const * __restrict__ blob, uint6
 
   if( portable ) { pstat[j] = FD_PT_OK; return; }
 
-  /* small order: [8]P == identity by limb equality */
-  fe X2 = x, Y2 = y, Z2 = Z, r[4];
-  for( int it=0; it<2; it++ ) {
-    fd_small_dbl( r, X2, Y2, Z2 );
-    fd_fe_mul( X2, r[0], r[3] ); fd_fe_mul( Y2, r[1], r[2] ); fd_fe_mul( Z2, r[2], r[3] );
-  }
-  fd_small_dbl( r, X2, Y2, Z2 );
-  fe tX, tY, tZ;
-  fd_fe_mul( tX, r[0], r[3] ); fd_fe_mul( tY, r[1], r[2] ); fd_fe_mul( tZ, r[2], r[3] );
-  /* is_identity (fd_ed25519_ge.c:41-59): mul(X,1)==mul(0,Z), mul(Y,1)==mul(1,Z) */
-  fe one, zero, c0, c1; fd_fe_set( one, 1 ); fd_fe_set( zero, 0 );
-  fd_fe_mul_scalar( c0, tX, one ); fd_fe_mul_scalar( c1, zero, tZ );
-  int ix = fd_limbs_eq( c0, c1 );
-  fd_fe_mul_scalar( c0, tY, one ); fd_fe_mul_scalar( c1, one, tZ );
-  int iy = fd_limbs_eq( c0, c1 );
-  pstat[j] = (ix & iy) ? FD_PT_SMALL : FD_PT_OK;
+  /* small order (fd_ed25519_ge.c:21-66): the reference's [8]P limb test
+     flags exactly the 14 small-order encodings, so it is read off the
+     encoding (fd_ed25519_gpu_smallorder.h) */
+  pstat[j] = fd_enc_is_small_order( w ) ? FD_PT_SMALL : FD_PT_OK;
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -679,11 +656,7 @@ fd_k_dsm( uint64_t n, int32_t const * __restrict__ status, int32_t const * __res
   }
 
   /* Ai = {A,3A,...,15A} cached (avx/fd_ed25519_ge.c:423-481) */
-  fe4 d111;
-#pragma unroll
-  for( int l=0; l<3; l++ ) fd_fe_set( d111.l[l], 1 );
-  d111.l[3] = FD_GPU_D2;
-  v_mul( vu, vr, d111 ); v_subadd_12( vu );
+  v_mul_d111( vu, vr ); v_subadd_12( vu );
   fd_tab_store( tab, ii, 0, vu );
   v_p2_dbl( vt, vr.l[2], vr.l[1], vr.l[0] );
   {
@@ -700,7 +673,7 @@ fd_k_dsm( uint64_t n, int32_t const * __restrict__ status, int32_t const * __res
     a.l[0]=vt.l[2]; a.l[1]=vt.l[3]; a.l[2]=vt.l[2]; a.l[3]=vt.l[1];
     b.l[0]=vt.l[3]; b.l[1]=vt.l[1]; b.l[2]=vt.l[0]; b.l[3]=vt.l[0];
     v_mul( vt, a, b );
-    v_mul( vu, vt, d111 ); v_subadd_12( vu );
+    v_mul_d111( vu, vt ); v_subadd_12( vu );
     fd_tab_store( tab, ii, e+1, vu );
   }
 
@@ -1652,11 +1625,7 @@ fd_k_dsm_setup( uint64_t n, int32_t const * __restrict__ status, int32_t const *
   }
   /* non-pending signatures run on their (unused) inputs: their entries are
      never read */
-  fe4 d111;
-#pragma unroll
-  for( int l=0; l<3; l++ ) fd_fe_set( d111.l[l], 1 );
-  d111.l[3] = FD_GPU_D2;
-  v_mul( vu, vr, d111 ); v_subadd_12( vu );
+  v_mul_d111( vu, vr ); v_subadd_12( vu );
   fd_tab_store_rows( tab, n, i0, 0, vu, st, lane );
   v_p2_dbl( vt, vr.l[2], vr.l[1], vr.l[0] );
   {
@@ -1673,7 +1642,7 @@ fd_k_dsm_setup( uint64_t n, int32_t const * __restrict__ status, int32_t const *
     a.l[0]=vt.l[2]; a.l[1]=vt.l[3]; a.l[2]=vt.l[2]; a.l[3]=vt.l[1];
     b.l[0]=vt.l[3]; b.l[1]=vt.l[1]; b.l[2]=vt.l[0]; b.l[3]=vt.l[0];
     v_mul( vt, a, b );
-    v_mul( vu, vt, d111 ); v_subadd_12( vu );
+    v_mul_d111( vu, vt ); v_subadd_12( vu );
     fd_tab_store_rows( tab, n, i0, e+1, vu, st, lane );
   }
 }
@@ -1930,10 +1899,17 @@ fd_k_dsm_pool( uint64_t n, int32_t const * __restrict__ status, int32_t const * 
       if( kind ) {
         fe4 vt; fd_pool_ld( vt, L, s );
 #ifdef FD_POOL_TRAFFIC_DIAG
-        /* diagnostic builds only (tools/pmc_pool_split.sh): every Ai read
-           hits signature 0's entries (cache resident), so the HBM bytes
-           that disappear are the Ai-entry reads; codes are wrong */
-        fd_pool_add( vt, op, tab, FD_TAB_ENTRY, fd_gpu_bi_tab );
+        /* diagnostic builds only: every Ai read hits the entries of one of
+           the first 1,024 signatures (1.5 MiB, L2 resident), so the HBM
+           bytes that disappear are the Ai-entry reads while the lanes'
+           operands stay distinct (reading signature 0's entries everywhere
+           also made all 64 lanes multiply by the same values, which alone
+           raises the clock).  Slot s of wave gw takes table (gw + s) & 1023:
+           sg & 1023 would be gw & 1023 for every slot of a wave whenever
+           nwaves is a multiple of 1,024 (8,192 at 1,048,576 signatures),
+           one table per wave again.  Codes are wrong */
+        uint64_t sd = (uint64_t)((gw + s) & 1023u);
+        fd_pool_add( vt, op, tab + (sd < n ? sd : sg)*FD_TAB_ENTRY, n*FD_TAB_ENTRY, fd_gpu_bi_tab );
 #else
         fd_pool_add( vt, op, tab + sg*FD_TAB_ENTRY, n*FD_TAB_ENTRY, fd_gpu_bi_tab );
 #endif
