@@ -168,6 +168,8 @@ def lib() -> ctypes.CDLL:
         L.fd_vt_tcache_delete.restype = None
         L.fd_ed25519_gpu_debug_k.argtypes = [vp, ul, vp, ul, vp, vp, vp]
         L.fd_ed25519_gpu_debug_k.restype = ip
+        L.fd_ed25519_gpu_debug_verify_dig.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp, vp]
+        L.fd_ed25519_gpu_debug_verify_dig.restype = ip
         L.fd_ed25519_gpu_debug_fe.argtypes = [vp, ip, ul, vp, vp, vp]
         L.fd_ed25519_gpu_debug_fe.restype = ip
         L.fd_ed25519_gpu_sha512_packed.argtypes = [vp, ul, vp, ul, vp, vp, ip]
@@ -406,6 +408,26 @@ class Engine:
         if err:
             raise EngineError(f"debug_k: {strerror(err)}: {last_error()}")
         return k, st
+
+    def debug_verify_dig(self, blob: np.ndarray, desc: np.ndarray, dig: np.ndarray):
+        """Diagnostics (fd_ed25519_gpu_debug_verify_dig): the verify pipeline with each
+        signature's 64-byte digest given (dig, [n,64] uint8: what the reference
+        feeds fd_ed25519_sc_reduce) in place of SHA-512(R||A||M), on the schedule
+        the engine's mode and knobs give a batch of n -> (codes[n], k[n,32], status[n]);
+        k and status as debug_k."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        dig = np.ascontiguousarray(dig, dtype=np.uint8)
+        n = len(desc)
+        if dig.size != 64 * n:
+            raise EngineError(f"debug_verify_dig: dig holds {dig.size} bytes, not 64 per signature ({64 * n})")
+        codes = np.zeros(n, np.int32)
+        k = np.zeros((n, 32), np.uint8)
+        st = np.zeros(n, np.int32)
+        err = lib().fd_ed25519_gpu_debug_verify_dig(self._h, n, _p(blob), blob.nbytes, _p(desc), _p(dig), _p(codes), _p(k), _p(st))
+        if err:
+            raise EngineError(f"debug_verify_dig: {strerror(err)}: {last_error()}")
+        return codes, k, st
 
     def debug_fe(self, op: int, f: np.ndarray, g: np.ndarray) -> np.ndarray:
         """Diagnostics: the device field products (fd_k_debug_fe op 0-6, op 7 the oct DSM's half product) of

@@ -1170,6 +1170,92 @@ done:
   return err;
 }
 
+/* Diagnostics: the verify pipeline with each signature's 64-byte digest
+   given by the caller (dig, n x 64 bytes: what the reference hands to
+   fd_ed25519_sc_reduce, fd_ed25519_user.c:411-414) in place of
+   SHA-512(R||A||M) -- so k is the caller's choice and a test can build a
+   valid signature at any (S, k).  Everything else is the product path: S
+   check, decompression, small-order flags, the DSM of the schedule the
+   engine's mode and knobs give a batch of n (as fd_ed25519_gpu_launch_front
+   / _back choose it), compare, code precedence, ERR_ARG for descriptors
+   outside the blob.  The message bytes are not read.  fd_k_prep_dig takes
+   SHA-512 state words, so digest byte 8j+b becomes bits 56-8b.. of word j.
+   codes_out receives n codes; k_out (n x 32 bytes) and status_out as in
+   fd_ed25519_gpu_debug_k, either may be NULL.  Synchronous; host buffers. */
+extern "C" int fd_ed25519_gpu_debug_verify_dig( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
+                                                fd_ed25519_gpu_desc_t const * desc, uint8_t const * dig, int * codes_out,
+                                                uint8_t * k_out, int * status_out ) {
+  if( !g || n > g->max_sigs || blob_sz > g->max_blob || (n && (!desc || !dig || !codes_out)) || (blob_sz && !blob) )
+    return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  fd_knobs kn = fd_knobs_get( g );     /* before the locks below: fd_knobs_get takes g->lock itself */
+  /* both engine locks, dev_lock first (fd_ed25519_gpu_debug_k) */
+  std::lock_guard<std::mutex> dguard( g->dev_lock );
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
+  if( !sl ) return FD_ED25519_ERR_ARG;
+  hipStream_t st = sl->stream;
+  unsigned long doff = fd_desc_off( blob_sz );
+  memcpy( sl->h_blob, blob, blob_sz );
+  memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
+  memcpy( sl->h_blob + doff, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
+  fd_ed25519_gpu_desc_t const * d_desc = (fd_ed25519_gpu_desc_t const *)(sl->d_blob + doff);
+  fd_ed25519_gpu_work_t const * w = &g->dev_work[0];
+  /* host and device scratch: state words [n][8], k [4][n], codes [n] (the
+     working set's table scratch is the DSM's here) */
+  unsigned long const o_k = 64UL * n, o_c = 96UL * n, sz = 100UL * n, o_st = sz;   /* the host copy holds prep's status too */
+  uint8_t * h = (uint8_t *)malloc( sz + 4UL * n );
+  uint8_t * d = NULL;
+  int err = 0;
+  if( !h ) return FD_ED25519_ERR_GPU;
+  if( (e = hipMalloc( (void **)&d, sz )) != hipSuccess ) { free( h ); return fd_gpu_fail( "debug_verify_dig alloc", e ); }
+  {
+    uint64_t * hw = (uint64_t *)h;
+    for( unsigned long i=0; i<8UL*n; i++ ) {
+      uint64_t x = 0UL;
+      for( int b=0; b<8; b++ ) x = (x << 8) | (uint64_t)dig[8UL*i + (unsigned long)b];
+      hw[i] = x;
+    }
+  }
+  if( (e = fd_dev_serial_begin( g, st )) != hipSuccess
+   || (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, doff + n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess
+   || (e = hipMemcpyAsync( d, h, 64UL * n, hipMemcpyHostToDevice, st )) != hipSuccess
+   || (e = hipMemsetAsync( d + o_k, 0, 32UL * n, st )) != hipSuccess
+   || (e = hipMemsetAsync( d + o_c, 0x7f, 4UL * n, st )) != hipSuccess       /* no code: a row the DSM left unwritten shows */
+   || (e = fd_ed25519_gpu_launch_front_dig( n, sl->d_blob, blob_sz, d_desc, (uint64_t const *)d, w, (uint64_t *)(d + o_k), st,
+                                            kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )) != hipSuccess
+   || (e = hipMemcpyAsync( h + o_st, w->status, 4UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess   /* prep's, before the DSM settles it */
+   || (e = fd_ed25519_gpu_launch_back( n, sl->d_blob, d_desc, w, (int32_t *)(d + o_c), st, NULL,
+                                       kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )) != hipSuccess
+   || (e = hipMemcpyAsync( h + o_k, d + o_k, 36UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess
+   || (e = hipEventRecord( sl->done, st )) != hipSuccess
+   || (e = fd_dev_serial_end( g, st )) != hipSuccess ) { err = fd_gpu_fail( "debug_verify_dig", e ); (void)hipStreamSynchronize( st ); goto done; }
+  if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) {
+    sl->ticket = g->next_ticket++; sl->orphan = 1;
+    free( h );
+    return err;     /* the device buffer may still be in use: leaked */
+  }
+  {
+    int32_t const *  h_st = (int32_t const *)(h + o_st);
+    uint64_t const * h_k  = (uint64_t const *)(h + o_k);
+    memcpy( codes_out, h + o_c, 4UL * n );
+    for( unsigned long i=0; i<n; i++ ) {
+      if( status_out ) status_out[i] = h_st[i];
+      if( k_out )
+        for( int j=0; j<4; j++ ) {
+          uint64_t x = h_st[i] == 1 ? h_k[(unsigned long)j*n + i] : 0UL;
+          for( int b=0; b<8; b++ ) k_out[32UL*i + 8UL*(unsigned long)j + (unsigned long)b] = (uint8_t)(x >> (8*b));
+        }
+    }
+  }
+done:
+  hipFree( d );
+  free( h );
+  return err;
+}
+
 /* SHA-512 / SHA-384 of n messages blob[msg_off..+msg_sz) (sig_off and
    pub_off unused) on the device; hash_out receives n digests of 64 (48)
    bytes back to back.  Synchronous. */

@@ -2085,14 +2085,17 @@ fd_k_sha512_stream( uint32_t n, uint64_t * __restrict__ st, uint8_t const * __re
   for( int j=0; j<8; j++ ) st[8u*i + (uint32_t)j] = s[j];
 }
 
-/* fd_k_prep with the digests from the stream's chaining states */
+/* fd_k_prep with the digests from the stream's chaining states (or, for
+   fd_ed25519_gpu_debug_verify_dig, the caller's digests as state words);
+   sigmajor: signature-major op rows, zeroed here, for the quad / oct DSM;
+   kout (diagnostics, may be NULL): each pending signature's k, [4][n] */
 extern "C" __global__ void __launch_bounds__(256)
 fd_k_prep_dig( uint64_t n, uint8_t const * __restrict__ blob, uint64_t blob_sz, fd_ed25519_gpu_desc_t const * __restrict__ desc,
                uint64_t const * __restrict__ dig, int32_t * __restrict__ status, uint8_t * __restrict__ ops,
-               int32_t * __restrict__ op_start, int strict ) {
+               int32_t * __restrict__ op_start, int strict, int sigmajor, uint64_t * __restrict__ kout ) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[4*FD_SHA_STAGE_BYTES];   /* the recoder's digit slots */
   fd_prep_body_t<1>( (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, n, blob, blob_sz, desc, status, ops, op_start, strict,
-                     (fd_lds_u8 *)stage, NULL, 0, dig );
+                     (fd_lds_u8 *)stage, kout, sigmajor, dig );
 }
 
 extern "C" hipError_t fd_ed25519_gpu_launch_sha512_stream( uint32_t n, uint64_t * st, uint8_t const * data,
@@ -2107,19 +2110,10 @@ extern "C" hipError_t fd_ed25519_gpu_launch_sha512_stream( uint32_t n, uint64_t 
 extern "C" hipError_t fd_ed25519_gpu_launch_long( uint64_t n, uint8_t const * blob, uint64_t blob_sz, fd_ed25519_gpu_desc_t const * desc,
                                                   uint64_t const * st, fd_ed25519_gpu_work_t const * w, int32_t * out,
                                                   hipStream_t stream, int mode ) {
-  if( !n ) return hipSuccess;
-  mode &= 0xff;
-  int portable = mode == FD_ED25519_GPU_MODE_PORTABLE;
-  int strict   = mode == FD_ED25519_GPU_MODE_STRICT;
-  unsigned nb  = (unsigned)((n + 255) / 256);
-  unsigned nb2 = (unsigned)(((portable ? n : 2*n) + 255) / 256);
-  hipError_t e = hipMemsetAsync( w->ops, 0, (size_t)FD_OPS_MAX * n, stream );
+  /* no batch size reaches the pooled, quad or oct schedule with these knobs */
+  hipError_t e = fd_ed25519_gpu_launch_front_dig( n, blob, blob_sz, desc, st, w, NULL, stream, mode, ~0UL, 0UL, 0UL );
   if( e != hipSuccess ) return e;
-  hipLaunchKernelGGL( fd_k_prep_dig, dim3(nb), dim3(256), 0, stream, n, blob, blob_sz, desc, st, w->status, w->ops, w->op_start, strict );
-  hipLaunchKernelGGL( fd_k_decomp, dim3(nb2), dim3(256), 0, stream, n, blob, blob_sz, desc, w->status, w->pstat, w->pts, portable, strict );
-  hipLaunchKernelGGL( fd_k_dsm, dim3(nb), dim3(256), 0, stream, n, w->status, w->pstat, w->pts, w->ops, w->op_start, w->tab, out,
-                      blob, desc, portable, strict );
-  return hipGetLastError();
+  return fd_ed25519_gpu_launch_back( n, blob, desc, w, out, stream, NULL, mode, ~0UL, 0UL, 0UL );
 }
 
 /* ------------------------------------------------------------------ */
@@ -2179,6 +2173,36 @@ extern "C" hipError_t fd_ed25519_gpu_launch_front( uint64_t n, uint8_t const * b
   if( n >= pool_min )
     hipLaunchKernelGGL( fd_k_dsm_setup, dim3(nb), dim3(256), 0, stream, n, w->status, w->pstat, w->pts, w->tab, portable );
   if( ev ) hipEventRecord( ev[3], stream );   /* setup reads 0 on the other schedules */
+  return hipGetLastError();
+}
+
+/* fd_ed25519_gpu_launch_front with the digests of R || A || M given (dig:
+   [n][8] SHA-512 state words) instead of hashed: fd_k_prep_dig in place of
+   fd_k_prep, and on the quad / oct schedule in place of fd_k_front's prep
+   blocks (signature-major rows; fd_k_decomp then decompresses every
+   point, as fd_k_front's decomp blocks do).  The long-message path and the
+   chosen-digest diagnostics (fd_ed25519_gpu_debug_verify_dig; kout: each
+   pending signature's k as [4][n] words, may be NULL). */
+extern "C" hipError_t fd_ed25519_gpu_launch_front_dig( uint64_t n, uint8_t const * blob, uint64_t blob_sz, fd_ed25519_gpu_desc_t const * desc,
+                                                       uint64_t const * dig, fd_ed25519_gpu_work_t const * w, uint64_t * kout,
+                                                       hipStream_t stream, int mode, uint64_t pool_min, uint64_t quad_max, uint64_t oct_max ) {
+  if( !n ) return hipSuccess;
+  mode &= 0xff;
+  int portable = mode == FD_ED25519_GPU_MODE_PORTABLE;
+  int strict   = mode == FD_ED25519_GPU_MODE_STRICT;
+  unsigned nb  = (unsigned)((n + 255) / 256);
+  unsigned nb2 = (unsigned)(((portable ? n : 2*n) + 255) / 256);
+  int quad = n < pool_min && !portable && (n <= quad_max || n <= oct_max);
+  if( !quad ) {
+    hipError_t e = hipMemsetAsync( w->ops, 0, (size_t)FD_OPS_MAX * n, stream );
+    if( e != hipSuccess ) return e;
+  }
+  hipLaunchKernelGGL( fd_k_prep_dig, dim3(nb), dim3(256), 0, stream, n, blob, blob_sz, desc, dig, w->status, w->ops, w->op_start, strict,
+                      quad, kout );
+  hipLaunchKernelGGL( fd_k_decomp, dim3(nb2), dim3(256), 0, stream, n, blob, blob_sz, desc, quad ? (int32_t const *)NULL : w->status,
+                      w->pstat, w->pts, portable, strict );
+  if( n >= pool_min )
+    hipLaunchKernelGGL( fd_k_dsm_setup, dim3(nb), dim3(256), 0, stream, n, w->status, w->pstat, w->pts, w->tab, portable );
   return hipGetLastError();
 }
 

@@ -95,6 +95,13 @@ hipError_t fd_ed25519_gpu_launch_sha512_stream( uint32_t n, uint64_t * st, uint8
 hipError_t fd_ed25519_gpu_launch_long( uint64_t n, uint8_t const * blob, uint64_t blob_sz, fd_ed25519_gpu_desc_t const * desc,
                                        uint64_t const * st, fd_ed25519_gpu_work_t const * w, int32_t * out, hipStream_t stream,
                                        int mode );
+/* fd_ed25519_gpu_launch_front with the digests given as SHA-512 state
+   words dig[8 i .. 8 i + 8) instead of hashed (every schedule; no timing
+   events); kout as in fd_ed25519_gpu_launch_prep_k, or NULL.  Followed by
+   fd_ed25519_gpu_launch_back with the same mode and knobs. */
+hipError_t fd_ed25519_gpu_launch_front_dig( uint64_t n, uint8_t const * blob, uint64_t blob_sz, fd_ed25519_gpu_desc_t const * desc,
+                                            uint64_t const * dig, fd_ed25519_gpu_work_t const * w, uint64_t * kout,
+                                            hipStream_t stream, int mode, uint64_t pool_min, uint64_t quad_max, uint64_t oct_max );
 /* descriptor bounds: R||S, the key and the message inside blob[0, blob_sz)
    (64-bit sums, so no offset wraps) */
 static inline __host__ __device__ int fd_desc_in( fd_ed25519_gpu_desc_t const & d, uint64_t blob_sz ) {

@@ -21,6 +21,36 @@ extern "C" {
    ring lock.  Returns the number of slots written. */
 int fd_ed25519_gpu_slot_states( fd_ed25519_gpu_t * gpu, int * out, int max );
 
+/* Verify n signatures with each one's 64-byte digest supplied by the
+   caller in place of SHA-512(R || A || M): dig[64 i .. 64 i + 64) is the
+   byte string the reference hands to fd_ed25519_sc_reduce
+   (fd_ed25519_user.c:411-414), i.e. the digest in SHA-512's output byte
+   order, read as a 512-bit little-endian integer and reduced mod L to give
+   k.  (The host turns it into the chaining-state words fd_k_prep_dig
+   loads: word j is the big-endian read of bytes 8j .. 8j+7.)  The message
+   bytes are not read; msg_sz may be 0.
+
+   Everything after the digest is the product path: the S range check,
+   point decompression, the small-order flags, the double-scalar
+   multiplication on the schedule (uniform, pooled, quad, oct) that the
+   engine's mode and dsm_pool_min / dsm_quad_max / dsm_oct_max knobs give
+   a batch of n, the compare and the code precedence, with ERR_ARG for
+   descriptors outside the blob.  With k chosen freely a harness can build
+   a valid signature at any (S, k): pick a, set A = [a]B and
+   R = [S - k a mod L]B.
+
+   blob / desc as fd_ed25519_gpu_verify_packed (host memory).  codes_out
+   receives n codes.  k_out (n x 32 bytes) receives k little endian and
+   status_out[i] is 1 for the signatures still pending after the S check;
+   the others (and malformed descriptors) get 32 zero bytes and a status
+   != 1, as fd_ed25519_gpu_debug_k reports them.  k_out and status_out may
+   be NULL.  Synchronous.  Returns 0, FD_ED25519_ERR_ARG (NULL arguments,
+   n > max_sigs, blob_sz > max_blob) or FD_ED25519_ERR_GPU; n == 0 returns
+   0 and writes nothing. */
+int fd_ed25519_gpu_debug_verify_dig( fd_ed25519_gpu_t * gpu, unsigned long n, void const * blob, unsigned long blob_sz,
+                                     fd_ed25519_gpu_desc_t const * desc, unsigned char const * dig,
+                                     int * codes_out, unsigned char * k_out, int * status_out );
+
 #ifdef __cplusplus
 }
 #endif
