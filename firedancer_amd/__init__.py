@@ -31,6 +31,9 @@ MODE_STRICT = 2     # AVX checks with Q1-Q3 fixed (no reference build; SURVEY 8f
 
 
 DESC_DTYPE = np.dtype([("sig_off", "<u4"), ("pub_off", "<u4"), ("msg_off", "<u4"), ("msg_sz", "<u4")])
+# fd_ed25519_gpu_sign_desc_t; pub_off = SIGN_DERIVE: the key is derived from the seed on the device
+SIGN_DESC_DTYPE = np.dtype([("seed_off", "<u4"), ("pub_off", "<u4"), ("msg_off", "<u4"), ("msg_sz", "<u4")])
+SIGN_DERIVE = 0xFFFFFFFF
 
 _lib = None
 
@@ -240,6 +243,20 @@ def lib() -> ctypes.CDLL:
         L.fd_sha512_gpu_batch_fini.restype = vp
         L.fd_sha512_gpu_batch_abort.argtypes = [vp]
         L.fd_sha512_gpu_batch_abort.restype = vp
+        L.fd_ed25519_gpu_public_packed.argtypes = [vp, ul, vp, vp]
+        L.fd_ed25519_gpu_public_packed.restype = ip
+        L.fd_ed25519_gpu_sign_packed.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp]
+        L.fd_ed25519_gpu_sign_packed.restype = ip
+        L.fd_ed25519_gpu_sign_dev.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp, vp]
+        L.fd_ed25519_gpu_sign_dev.restype = ip
+        L.fd_ed25519_gpu_sign_batch.argtypes = [vp, ul, vp, vp, vp, vp, vp, vp, ip]
+        L.fd_ed25519_gpu_sign_batch.restype = ip
+        L.fd_ed25519_sign_batch_gpu.argtypes = [ul, vp, vp, vp, vp, vp, vp, ip]
+        L.fd_ed25519_sign_batch_gpu.restype = ip
+        L.fd_ed25519_gpu_debug_sign_op.argtypes = [vp, ip, ul, vp, vp, vp, vp]
+        L.fd_ed25519_gpu_debug_sign_op.restype = ip
+        L.fd_ed25519_gpu_sign_set_batch_inv.argtypes = [ip]
+        L.fd_ed25519_gpu_sign_set_batch_inv.restype = ip
         _lib = L
     return _lib
 
@@ -441,6 +458,53 @@ class Engine:
         if err:
             raise EngineError(f"debug_fe: {strerror(err)}: {last_error()}")
         return h
+
+    def sign_packed(self, blob: np.ndarray, sdesc: np.ndarray, want_pub: bool = True):
+        """Sign a packed batch (fd_ed25519_gpu_sign_packed): sdesc is SIGN_DESC_DTYPE
+        (seed_off, pub_off or SIGN_DERIVE, msg_off, msg_sz) -> (sig[n,64], pub[n,32] or
+        None, codes[n]); an out-of-bounds entry gets ERR_ARG and zero bytes."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        sdesc = np.ascontiguousarray(sdesc, dtype=SIGN_DESC_DTYPE)
+        n = len(sdesc)
+        sig = np.zeros((n, 64), np.uint8)
+        pub = np.zeros((n, 32), np.uint8) if want_pub else None
+        codes = np.zeros(n, np.int32)
+        err = lib().fd_ed25519_gpu_sign_packed(self._h, n, _p(blob), blob.nbytes, _p(sdesc), _p(sig),
+                                               _p(pub) if want_pub else None, _p(codes))
+        if err:
+            raise EngineError(f"sign_packed: {strerror(err)}: {last_error()}")
+        return sig, pub, codes
+
+    def public_from_seeds(self, seeds: np.ndarray) -> np.ndarray:
+        """Public keys [n,32] of seeds [n,32], derived on the device."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1, 32)
+        pub = np.zeros((len(seeds), 32), np.uint8)
+        err = lib().fd_ed25519_gpu_public_packed(self._h, len(seeds), _p(seeds), _p(pub))
+        if err:
+            raise EngineError(f"public_from_seeds: {strerror(err)}: {last_error()}")
+        return pub
+
+    def sign_dev(self, n: int, d_blob: int, blob_sz: int, d_sdesc: int, d_sig_out: int, d_pub_out: int, d_out: int,
+                 stream: int = 0) -> None:
+        """Device-resident signing (raw device pointers; d_pub_out may be 0), ordered on
+        `stream` as verify_dev.  The caller's memory: seeds in d_blob are not cleared."""
+        err = lib().fd_ed25519_gpu_sign_dev(self._h, n, d_blob, blob_sz, d_sdesc, d_sig_out, d_pub_out or None, d_out,
+                                            stream or None)
+        if err:
+            raise EngineError(f"sign_dev: {strerror(err)}: {last_error()}")
+
+    def debug_sign_op(self, op: int, in0: np.ndarray, in1: np.ndarray = None, in2: np.ndarray = None) -> np.ndarray:
+        """Diagnostics (fd_ed25519_gpu_debug_sign_op): op 0, the encodings of [s]B for
+        scalars in0 [n,32]; op 1, (k a + r) mod L for k = in0, a = in1, r = in2 -> [n,32]."""
+        a = [None if x is None else np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 32) for x in (in0, in1, in2)]
+        n = len(a[0])
+        if any(x is not None and len(x) != n for x in a):
+            raise EngineError("debug_sign_op: operands differ in length")
+        out = np.zeros((n, 32), np.uint8)
+        err = lib().fd_ed25519_gpu_debug_sign_op(self._h, int(op), n, *[None if x is None else _p(x) for x in a], _p(out))
+        if err:
+            raise EngineError(f"debug_sign_op: {strerror(err)}: {last_error()}")
+        return out
 
     def sha512(self, msgs, is384: bool = False) -> list:
         """SHA-512 (SHA-384) digests of byte strings on the device."""
@@ -817,4 +881,21 @@ def sign_batch(seeds: np.ndarray, blob: np.ndarray, msg_off: np.ndarray, msg_sz:
     pub = np.zeros((n, 32), np.uint8)
     sig = np.zeros((n, 64), np.uint8)
     lib().fd_ed25519_sign_batch(n, _p(seeds), _p(blob), _p(msg_off), _p(msg_sz), _p(pub), _p(sig), nthreads)
+    return pub, sig
+
+
+def sign_batch_gpu(seeds: np.ndarray, blob: np.ndarray, msg_off: np.ndarray, msg_sz: np.ndarray, engine: Engine = None):
+    """sign_batch on the GPU (fd_ed25519_gpu_sign_batch; engine None: the process-default
+    engine), keys derived on the device: returns (pub[n,32], sig[n,64])."""
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1, 32)
+    n = len(seeds)
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64)
+    msg_sz = np.ascontiguousarray(msg_sz, dtype=np.uint32)
+    pub = np.zeros((n, 32), np.uint8)
+    sig = np.zeros((n, 64), np.uint8)
+    err = lib().fd_ed25519_gpu_sign_batch(engine._h if engine is not None else None, n, _p(seeds), _p(blob), _p(msg_off),
+                                          _p(msg_sz), _p(pub), _p(sig), 1)
+    if err:
+        raise EngineError(f"sign_batch_gpu: {strerror(err)}: {last_error()}")
     return pub, sig

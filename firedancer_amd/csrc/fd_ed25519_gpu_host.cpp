@@ -27,6 +27,7 @@
 #include <map>
 #include "fd_ed25519_gpu_private.h"
 #include "fd_ed25519_gpu_diag.h"
+#include "fd_ed25519_gpu_sign_private.h"
 
 #define FD_GPU_DEPTH_DEFAULT 3
 #define FD_GPU_DEPTH_MAX     8
@@ -166,6 +167,7 @@ struct fd_ed25519_gpu_slot {
   int                     early;    /* codes go straight to h_out over a sentinel: a blocking poll may take them as they land */
   int                     retiring; /* its codes were taken early: reclaimed once its event completes */
   uint8_t *               h_dig;    /* pinned digests (SHA-512 batch), allocated on first use */
+  uint8_t *               h_sgn;    /* pinned signing results (100 B per signature), allocated on first use */
 };
 
 struct fd_ed25519_gpu {
@@ -445,6 +447,7 @@ extern "C" void fd_ed25519_gpu_delete( fd_ed25519_gpu_t * g ) {
     if( sl->h_desc ) hipHostFree( sl->h_desc );
     if( sl->h_out  ) hipHostFree( sl->h_out );
     if( sl->h_dig  ) hipHostFree( sl->h_dig );
+    if( sl->h_sgn  ) hipHostFree( sl->h_sgn );
     if( sl->d_blob ) hipFree( sl->d_blob );
     if( sl->d_desc ) hipFree( sl->d_desc );
     if( sl->d_out  ) hipFree( sl->d_out );
@@ -1686,4 +1689,190 @@ extern "C" char const * fd_ed25519_strerror( int err ) {
   default: break;
   }
   return "unknown";
+}
+
+/* ------------------------------------------------------------------ */
+/* Batch signing and key derivation (include/fd_ed25519_gpu_sign.h). */
+
+static int fd_sgn_batch_inv = FD_SGN_BATCH_INV;
+
+extern "C" int fd_ed25519_gpu_sign_set_batch_inv( int on ) {
+  return __atomic_exchange_n( &fd_sgn_batch_inv, on ? 1 : 0, __ATOMIC_RELAXED );
+}
+
+/* per signature of a slot's working set (its table scratch, 1536 B per
+   signature): R || S, the key, the status */
+#define FD_SGN_OUT_PER_SIG 100UL
+
+/* Run one staged signing / derivation batch on a slot and collect its
+   100 n (sign) or 32 n (derive) result bytes in sl->h_sgn.  in_sz bytes of
+   sl->h_blob go to the device in one copy; whatever the outcome, the first
+   clear_sz bytes (where seeds may lie) of the device blob are cleared by the
+   slot's stream behind the kernel and those of the pinned blob by the
+   host.  Caller holds g->lock and has set the device. */
+static int fd_sgn_run( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n, unsigned long in_sz, unsigned long clear_sz,
+                       unsigned long blob_sz, unsigned long doff, int sign ) {
+  hipError_t e;
+  hipStream_t st = sl->stream;
+  int err = 0;
+  uint8_t * d_res = (uint8_t *)sl->work.tab;
+  unsigned long res_sz = ( sign ? FD_SGN_OUT_PER_SIG : 32UL ) * n;
+  int binv = __atomic_load_n( &fd_sgn_batch_inv, __ATOMIC_RELAXED );
+  if( !sl->h_sgn && (e = hipHostMalloc( (void **)&sl->h_sgn, g->max_sigs * FD_SGN_OUT_PER_SIG, hipHostMallocDefault )) != hipSuccess ) {
+    sl->h_sgn = NULL;
+    memset( sl->h_blob, 0, clear_sz );
+    return fd_gpu_fail( "hipHostMalloc signing results", e );
+  }
+  if( (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, in_sz, hipMemcpyHostToDevice, st )) != hipSuccess ) { err = fd_gpu_fail( "H2D signing batch", e ); goto drain; }
+  if( sign ) e = fd_ed25519_gpu_launch_sign( n, sl->d_blob, blob_sz, (fd_ed25519_gpu_sign_desc_t const *)(sl->d_blob + doff),
+                                             d_res, d_res + 64UL*n, (int32_t *)(d_res + 96UL*n), binv, st );
+  else       e = fd_ed25519_gpu_launch_public( n, sl->d_blob, d_res, 1, binv, st );
+  if( e != hipSuccess ) { err = fd_gpu_fail( "launch sign", e ); goto drain; }
+  if( (e = hipMemcpyAsync( sl->h_sgn, d_res, res_sz, hipMemcpyDeviceToHost, st )) != hipSuccess ) { err = fd_gpu_fail( "D2H signatures", e ); goto drain; }
+  if( (e = hipMemsetAsync( sl->d_blob, 0, clear_sz, st )) != hipSuccess ) { err = fd_gpu_fail( "clear seeds", e ); goto drain; }
+  if( (e = hipEventRecord( sl->done, st )) != hipSuccess ) { err = fd_gpu_fail( "event", e ); goto drain; }
+  err = fd_event_wait( sl->done, fd_timeout( g ) );
+  if( err ) { sl->ticket = g->next_ticket++; sl->orphan = 1; }   /* the stream still clears the device blob before the slot comes back */
+  memset( sl->h_blob, 0, clear_sz );
+  return err;
+drain:
+  /* part of the batch may be queued: let it finish, then clear both copies */
+  (void)hipStreamSynchronize( st );
+  (void)hipMemsetAsync( sl->d_blob, 0, clear_sz, st );
+  (void)hipStreamSynchronize( st );
+  (void)hipGetLastError();
+  memset( sl->h_blob, 0, clear_sz );
+  return err;
+}
+
+extern "C" int fd_ed25519_gpu_sign_packed( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
+                                           fd_ed25519_gpu_sign_desc_t const * sdesc, void * sig_out, void * pub_out_opt, int * out ) {
+  if( !g || n > g->max_sigs || blob_sz > g->max_blob || (n && (!sdesc || !sig_out || !out)) || (blob_sz && !blob) ) return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
+  if( !sl ) return FD_ED25519_ERR_ARG;
+  unsigned long doff = fd_desc_off( blob_sz );
+  if( sl->h_blob != blob ) memcpy( sl->h_blob, blob, blob_sz );
+  memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
+  memcpy( sl->h_blob + doff, sdesc, n * sizeof(fd_ed25519_gpu_sign_desc_t) );
+  int err = fd_sgn_run( g, sl, n, doff + n * sizeof(fd_ed25519_gpu_sign_desc_t), blob_sz, blob_sz, doff, 1 );
+  if( err ) return err;
+  memcpy( sig_out, sl->h_sgn, 64UL*n );
+  if( pub_out_opt ) memcpy( pub_out_opt, sl->h_sgn + 64UL*n, 32UL*n );
+  memcpy( out, sl->h_sgn + 96UL*n, 4UL*n );
+  sl->staged = 0;
+  return 0;
+}
+
+extern "C" int fd_ed25519_gpu_public_packed( fd_ed25519_gpu_t * g, unsigned long n, void const * seeds, void * pub_out ) {
+  if( !g || n > g->max_sigs || 32UL*n > g->blob_cap || (n && (!seeds || !pub_out)) ) return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
+  if( !sl ) return FD_ED25519_ERR_ARG;
+  memcpy( sl->h_blob, seeds, 32UL*n );
+  int err = fd_sgn_run( g, sl, n, 32UL*n, 32UL*n, 0UL, 0UL, 0 );
+  if( err ) return err;
+  memcpy( pub_out, sl->h_sgn, 32UL*n );
+  return 0;
+}
+
+extern "C" int fd_ed25519_gpu_sign_dev( fd_ed25519_gpu_t * g, unsigned long n, void const * d_blob, unsigned long blob_sz,
+                                        fd_ed25519_gpu_sign_desc_t const * d_sdesc, void * d_sig_out, void * d_pub_out_opt,
+                                        int * d_out, void * stream ) {
+  if( !g || n > (1UL<<31) || (n && (!d_blob || !d_sdesc || !d_sig_out || !d_out))
+      || ((uintptr_t)d_blob & 3UL) || ((uintptr_t)d_sig_out & 15UL) || ((uintptr_t)d_pub_out_opt & 15UL) ) return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  hipStream_t st = stream ? (hipStream_t)stream : g->slot[0].stream;
+  if( (e = fd_ed25519_gpu_launch_sign( n, (uint8_t const *)d_blob, blob_sz, d_sdesc, (uint8_t *)d_sig_out, (uint8_t *)d_pub_out_opt,
+                                       (int32_t *)d_out, __atomic_load_n( &fd_sgn_batch_inv, __ATOMIC_RELAXED ), st )) != hipSuccess )
+    return fd_gpu_fail( "fd_ed25519_gpu_launch_sign", e );
+  return 0;
+}
+
+extern "C" int fd_ed25519_gpu_debug_sign_op( fd_ed25519_gpu_t * g, int op, unsigned long n, void const * in0, void const * in1,
+                                             void const * in2, void * out ) {
+  if( !g || op < 0 || op > 1 || n > (1UL<<20) || (n && (!in0 || !out || (op == 1 && (!in1 || !in2)))) ) return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
+  if( !sl ) return FD_ED25519_ERR_ARG;
+  hipStream_t st = sl->stream;
+  unsigned long sz = 32UL * n;
+  uint8_t * d = NULL;
+  int err = 0;
+  if( (e = hipMalloc( (void **)&d, 4UL * sz )) != hipSuccess ) return fd_gpu_fail( "debug_sign_op alloc", e );
+  if( (e = hipMemcpyAsync( d, in0, sz, hipMemcpyHostToDevice, st )) != hipSuccess
+   || ( op == 1 && ( (e = hipMemcpyAsync( d + sz, in1, sz, hipMemcpyHostToDevice, st )) != hipSuccess
+                  || (e = hipMemcpyAsync( d + 2UL*sz, in2, sz, hipMemcpyHostToDevice, st )) != hipSuccess ) )
+   || (e = ( op == 0 ? fd_ed25519_gpu_launch_public( n, d, d + 3UL*sz, 0, __atomic_load_n( &fd_sgn_batch_inv, __ATOMIC_RELAXED ), st )
+                     : fd_ed25519_gpu_launch_debug_muladd( n, d, d + sz, d + 2UL*sz, d + 3UL*sz, st ) )) != hipSuccess
+   || (e = hipMemcpyAsync( out, d + 3UL*sz, sz, hipMemcpyDeviceToHost, st )) != hipSuccess
+   || (e = hipEventRecord( sl->done, st )) != hipSuccess ) { err = fd_gpu_fail( "debug_sign_op", e ); (void)hipStreamSynchronize( st ); }
+  else if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) {
+    sl->ticket = g->next_ticket++; sl->orphan = 1;
+    return err;     /* the buffer may still be in use: leaked */
+  }
+  hipFree( d );
+  return err;
+}
+
+/* fd_ed25519_sign_batch on an engine: consecutive elements are packed into
+   a slot's pinned blob (seed, the key if given, the message) until the
+   engine's max_sigs or max_blob is reached, signed as one packed batch and
+   scattered; an element that cannot fit a blob on its own goes to the host
+   routine. */
+extern "C" int fd_ed25519_gpu_sign_batch( fd_ed25519_gpu_t * g, unsigned long n, unsigned char const * seed, unsigned char const * blob,
+                                          uint64_t const * msg_off, uint32_t const * msg_sz, unsigned char * pub, unsigned char * sig,
+                                          int derive ) {
+  if( !g ) g = fd_default_engine();
+  if( !g ) return FD_ED25519_ERR_GPU;
+  if( n && (!seed || !msg_off || !msg_sz || !pub || !sig) ) return FD_ED25519_ERR_ARG;
+  unsigned long max_sigs = g->max_sigs, max_blob = g->max_blob;
+  unsigned long const fixed = derive ? 32UL : 64UL;
+  std::vector<int> codes( max_sigs < n ? max_sigs : n );
+  unsigned long i = 0;
+  while( i < n ) {
+    if( fixed + (unsigned long)msg_sz[i] > max_blob ) {
+      if( derive ) fd_ed25519_public_from_private( pub + 32UL*i, seed + 32UL*i, NULL );
+      fd_ed25519_sign( sig + 64UL*i, blob + msg_off[i], msg_sz[i], pub + 32UL*i, seed + 32UL*i, NULL );
+      i++;
+      continue;
+    }
+    void * sblob; fd_ed25519_gpu_desc_t * sdesc_;
+    int err = fd_stage_wait( g, &sblob, &sdesc_ );
+    if( err ) return err;
+    fd_ed25519_gpu_sign_desc_t * sd = (fd_ed25519_gpu_sign_desc_t *)sdesc_;
+    uint8_t * bl = (uint8_t *)sblob;
+    unsigned long used = 0, cnt = 0;
+    while( i + cnt < n && cnt < max_sigs && used + fixed + (unsigned long)msg_sz[i+cnt] <= max_blob ) {
+      unsigned long j = i + cnt;
+      memcpy( bl + used, seed + 32UL*j, 32UL );
+      sd[cnt].seed_off = (uint32_t)used; used += 32UL;
+      if( derive ) sd[cnt].pub_off = FD_ED25519_GPU_SIGN_DERIVE;
+      else { memcpy( bl + used, pub + 32UL*j, 32UL ); sd[cnt].pub_off = (uint32_t)used; used += 32UL; }
+      if( msg_sz[j] ) memcpy( bl + used, blob + msg_off[j], msg_sz[j] );
+      sd[cnt].msg_off = (uint32_t)used; sd[cnt].msg_sz = msg_sz[j]; used += msg_sz[j];
+      cnt++;
+    }
+    err = fd_ed25519_gpu_sign_packed( g, cnt, sblob, used, sd, sig + 64UL*i, derive ? pub + 32UL*i : NULL, codes.data() );
+    if( err ) { memset( bl, 0, used ); fd_ed25519_gpu_unstage( g, sblob ); return err; }
+    for( unsigned long k=0; k<cnt; k++ ) if( codes[k] ) return FD_ED25519_ERR_GPU;   /* descriptors built here are in bounds */
+    i += cnt;
+  }
+  return 0;
+}
+
+extern "C" int fd_ed25519_sign_batch_gpu( unsigned long n, unsigned char const * seed, unsigned char const * blob, uint64_t const * msg_off,
+                                          uint32_t const * msg_sz, unsigned char * pub, unsigned char * sig, int derive ) {
+  return fd_ed25519_gpu_sign_batch( NULL, n, seed, blob, msg_off, msg_sz, pub, sig, derive );
 }
