@@ -24,6 +24,7 @@ ERR_PUBKEY = -2
 ERR_MSG = -3
 ERR_ARG = -16
 ERR_GPU = -17
+ERR_TXN = -18       # FD_ED25519_ERR_TXN (fd_ed25519_gpu_txn.h): fd_txn_parse would return 0
 
 MODE_AVX = 0        # reference AVX2 build semantics (default)
 MODE_PORTABLE = 1   # reference FD_HAS_AVX=0 build semantics
@@ -34,6 +35,11 @@ DESC_DTYPE = np.dtype([("sig_off", "<u4"), ("pub_off", "<u4"), ("msg_off", "<u4"
 # fd_ed25519_gpu_sign_desc_t; pub_off = SIGN_DERIVE: the key is derived from the seed on the device
 SIGN_DESC_DTYPE = np.dtype([("seed_off", "<u4"), ("pub_off", "<u4"), ("msg_off", "<u4"), ("msg_sz", "<u4")])
 SIGN_DERIVE = 0xFFFFFFFF
+# fd_ed25519_gpu_txn_t: one transaction, payload = blob[off, off+sz)
+TXN_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4")])
+# fd_ed25519_gpu_txn_result_t
+TXN_RESULT_DTYPE = np.dtype([("status", "<i4"), ("sig_base", "<u4"), ("tag", "<u8"), ("footprint", "<u2"),
+                             ("reject_line", "<u2"), ("sig_cnt", "u1"), ("version", "u1"), ("_pad", "u1", (2,))])
 
 _lib = None
 
@@ -257,6 +263,16 @@ def lib() -> ctypes.CDLL:
         L.fd_ed25519_gpu_debug_sign_op.restype = ip
         L.fd_ed25519_gpu_sign_set_batch_inv.argtypes = [ip]
         L.fd_ed25519_gpu_sign_set_batch_inv.restype = ip
+        L.fd_ed25519_gpu_txns_reserve.argtypes = [vp, ul]
+        L.fd_ed25519_gpu_txns_reserve.restype = ip
+        L.fd_ed25519_gpu_verify_txns_dev.argtypes = [vp, ul, vp, ul, vp, ul, vp, vp, vp, ul, vp]
+        L.fd_ed25519_gpu_verify_txns_dev.restype = ip
+        L.fd_ed25519_gpu_verify_txns_dev_timed.argtypes = [vp, ul, vp, ul, vp, ul, vp, vp, vp, ul, vp, vp]
+        L.fd_ed25519_gpu_verify_txns_dev_timed.restype = ip
+        L.fd_ed25519_gpu_verify_txns_packed.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp, ul]
+        L.fd_ed25519_gpu_verify_txns_packed.restype = ip
+        L.fd_ed25519_gpu_debug_txn_descs.argtypes = [vp, ul, vp, ul, vp, ul, vp, ctypes.POINTER(ul), vp]
+        L.fd_ed25519_gpu_debug_txn_descs.restype = ip
         _lib = L
     return _lib
 
@@ -505,6 +521,74 @@ class Engine:
         if err:
             raise EngineError(f"debug_sign_op: {strerror(err)}: {last_error()}")
         return out
+
+    def txns_reserve(self, max_txn: int) -> None:
+        """Allocate the scratch of the transaction calls for batches of up to max_txn
+        transactions now (fd_ed25519_gpu_txns_reserve) instead of in the first call."""
+        err = lib().fd_ed25519_gpu_txns_reserve(self._h, int(max_txn))
+        if err:
+            raise EngineError(f"txns_reserve: {strerror(err)}: {last_error()}")
+
+    def verify_txns(self, blob: np.ndarray, txns: np.ndarray, want_codes: bool = False, txn_out_stride: int = 0):
+        """Whole transactions, host buffers (fd_ed25519_gpu_verify_txns_packed): txns is
+        TXN_DTYPE (payload t = blob[off, off+sz)) -> results (TXN_RESULT_DTYPE: status,
+        sig_base, tag, footprint, reject_line, sig_cnt, version), or the tuple (results,
+        codes, txn_out) when want_codes or txn_out_stride ask for more: codes the
+        per-signature codes at sig_base + i (else None), txn_out [n, stride] uint8 with
+        transaction t's fd_txn_t where 0 < footprint <= stride (zeros elsewhere; else None)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=TXN_DTYPE)
+        n = len(txns)
+        res = np.zeros(n, TXN_RESULT_DTYPE)
+        codes = np.zeros(127 * n, np.int32) if want_codes else None
+        out = np.zeros((n, txn_out_stride), np.uint8) if txn_out_stride else None
+        err = lib().fd_ed25519_gpu_verify_txns_packed(self._h, n, _p(blob), blob.nbytes, _p(txns), _p(res),
+                                                      _p(codes) if want_codes else None,
+                                                      _p(out) if txn_out_stride else None, txn_out_stride)
+        if err:
+            raise EngineError(f"verify_txns: {strerror(err)}: {last_error()}")
+        if not want_codes and not txn_out_stride:
+            return res
+        if want_codes:
+            got = res["sig_cnt"] > 0
+            n_sig = int((res["sig_base"][got].astype(np.int64) + res["sig_cnt"][got]).max()) if got.any() else 0
+            codes = codes[:n_sig].copy()
+        return res, codes, out
+
+    def verify_txns_dev(self, n_txn: int, d_blob: int, blob_sz: int, d_txn: int, sig_cap: int, d_res: int,
+                        d_codes: int = 0, d_txn_out: int = 0, txn_out_stride: int = 0, stream: int = 0,
+                        timed: bool = False):
+        """Device-resident transactions (fd_ed25519_gpu_verify_txns_dev; raw device
+        pointers, d_codes and d_txn_out may be 0), ordered on `stream` as verify_dev.
+        timed: block and return the four new kernels' durations (ms: parse, scan,
+        expand, reduce)."""
+        if timed:
+            ms = np.zeros(4, np.float32)
+            err = lib().fd_ed25519_gpu_verify_txns_dev_timed(self._h, n_txn, d_blob, blob_sz, d_txn, sig_cap, d_res, d_codes or None,
+                                                             d_txn_out or None, txn_out_stride, stream or None, _p(ms))
+        else:
+            ms = None
+            err = lib().fd_ed25519_gpu_verify_txns_dev(self._h, n_txn, d_blob, blob_sz, d_txn, sig_cap, d_res, d_codes or None,
+                                                       d_txn_out or None, txn_out_stride, stream or None)
+        if err:
+            raise EngineError(f"verify_txns_dev: {strerror(err)}: {last_error()}")
+        return ms
+
+    TXN_KERNELS = ("fd_k_txn_parse", "fd_k_txn_scan", "fd_k_txn_expand", "fd_k_txn_reduce")
+
+    def debug_txn_descs(self, blob: np.ndarray, txns: np.ndarray, sig_cap: int):
+        """Diagnostics (fd_ed25519_gpu_debug_txn_descs): parse, scan and expand only ->
+        (desc[sig_cap] as fd_k_txn_expand wrote every slot, n_sig, results)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=TXN_DTYPE)
+        desc = np.zeros(sig_cap, DESC_DTYPE)
+        res = np.zeros(len(txns), TXN_RESULT_DTYPE)
+        n_sig = ctypes.c_ulong(0)
+        err = lib().fd_ed25519_gpu_debug_txn_descs(self._h, len(txns), _p(blob), blob.nbytes, _p(txns), sig_cap, _p(desc),
+                                                   ctypes.byref(n_sig), _p(res))
+        if err:
+            raise EngineError(f"debug_txn_descs: {strerror(err)}: {last_error()}")
+        return desc, n_sig.value, res
 
     def sha512(self, msgs, is384: bool = False) -> list:
         """SHA-512 (SHA-384) digests of byte strings on the device."""

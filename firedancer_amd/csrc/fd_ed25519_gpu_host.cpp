@@ -28,6 +28,7 @@
 #include "fd_ed25519_gpu_private.h"
 #include "fd_ed25519_gpu_diag.h"
 #include "fd_ed25519_gpu_sign_private.h"
+#include "fd_ed25519_gpu_txn_private.h"
 
 #define FD_GPU_DEPTH_DEFAULT 3
 #define FD_GPU_DEPTH_MAX     8
@@ -170,6 +171,15 @@ struct fd_ed25519_gpu_slot {
   uint8_t *               h_sgn;    /* pinned signing results (100 B per signature), allocated on first use */
 };
 
+/* one of the two scratch sets of the transaction calls (fd_ed25519_gpu_txn.h) */
+struct fd_txn_set {
+  fd_txn_meta_t *         meta;    /* txn_cap entries */
+  uint32_t *              part;    /* fd_txn_part_cnt( txn_cap ) words */
+  fd_ed25519_gpu_desc_t * desc;    /* max_sigs slots */
+  int32_t *               codes;   /* max_sigs codes */
+  hipEvent_t              done;    /* the last call that used the set has finished with it */
+};
+
 struct fd_ed25519_gpu {
   int           device;
   unsigned long max_sigs;
@@ -207,6 +217,16 @@ struct fd_ed25519_gpu {
   unsigned long dev_stats_cnt;
   hipEvent_t    dev_ev[FD_DEV_STATS_MAX][FD_EV_CNT];
   hipEvent_t    kev[FD_EV_CNT];   /* per-kernel timing events */
+  /* whole transactions (fd_ed25519_gpu_txns_reserve; under dev_lock):
+     successive calls alternate between two scratch sets; the packed call
+     stages entries, results, codes and descriptors in txn_pk */
+  fd_txn_set    txn_set[2];
+  unsigned long txn_cap;          /* transactions the sets and the staging take */
+  unsigned long txn_seq;
+  uint8_t *     d_txn_pk;
+  uint8_t *     h_txn_pk;         /* pinned, the same layout */
+  unsigned long txn_pk_sz;
+  hipEvent_t    txn_ev[6];        /* per-kernel timing events of the transaction kernels */
   fd_ring_lock  lock;
 };
 
@@ -466,6 +486,17 @@ extern "C" void fd_ed25519_gpu_delete( fd_ed25519_gpu_t * g ) {
   if( g->dev_sf ) hipStreamDestroy( g->dev_sf );
   if( g->dev_sb ) hipStreamDestroy( g->dev_sb );
   for( int k=0; k<FD_EV_CNT; k++ ) if( g->kev[k] ) hipEventDestroy( g->kev[k] );
+  for( int b=0; b<2; b++ ) {
+    fd_txn_set * ts = &g->txn_set[b];
+    if( ts->meta  ) hipFree( ts->meta );
+    if( ts->part  ) hipFree( ts->part );
+    if( ts->desc  ) hipFree( ts->desc );
+    if( ts->codes ) hipFree( ts->codes );
+    if( ts->done  ) hipEventDestroy( ts->done );
+  }
+  if( g->d_txn_pk ) hipFree( g->d_txn_pk );
+  if( g->h_txn_pk ) hipHostFree( g->h_txn_pk );
+  for( int k=0; k<6; k++ ) if( g->txn_ev[k] ) hipEventDestroy( g->txn_ev[k] );
   delete g;
 }
 
@@ -1686,6 +1717,7 @@ extern "C" char const * fd_ed25519_strerror( int err ) {
   case FD_ED25519_ERR_MSG:    return "bad message";
   case FD_ED25519_ERR_ARG:    return "bad argument";
   case FD_ED25519_ERR_GPU:    return "gpu failure";
+  case FD_ED25519_ERR_TXN:    return "malformed transaction";
   default: break;
   }
   return "unknown";
@@ -1875,4 +1907,287 @@ extern "C" int fd_ed25519_gpu_sign_batch( fd_ed25519_gpu_t * g, unsigned long n,
 extern "C" int fd_ed25519_sign_batch_gpu( unsigned long n, unsigned char const * seed, unsigned char const * blob, uint64_t const * msg_off,
                                           uint32_t const * msg_sz, unsigned char * pub, unsigned char * sig, int derive ) {
   return fd_ed25519_gpu_sign_batch( NULL, n, seed, blob, msg_off, msg_sz, pub, sig, derive );
+}
+
+/* ------------------------------------------------------------------ */
+/* Whole transactions (include/fd_ed25519_gpu_txn.h). */
+
+static inline unsigned long fd_al16( unsigned long x ) { return (x + 15UL) & ~15UL; }
+
+/* the staging layout of the host-buffer calls (device and pinned alike):
+   entries | results | n_sig | codes or descriptors (max_sigs) | fd_txn_t rows */
+struct fd_txn_pk_off { unsigned long txn, res, nsig, sig, out; };
+static fd_txn_pk_off fd_txn_pk_layout( unsigned long cap, unsigned long max_sigs ) {
+  fd_txn_pk_off o;
+  o.txn  = 0UL;
+  o.res  = o.txn  + fd_al16( cap * sizeof(fd_ed25519_gpu_txn_t) );
+  o.nsig = o.res  + fd_al16( cap * sizeof(fd_ed25519_gpu_txn_result_t) );
+  o.sig  = o.nsig + 16UL;
+  o.out  = o.sig  + fd_al16( max_sigs * sizeof(fd_ed25519_gpu_desc_t) );
+  return o;
+}
+
+/* Scratch for n_txn transactions a call and out_sz bytes of fd_txn_t rows
+   in the staging.  Growing waits for the device to go idle first (earlier
+   calls may still use the old scratch).  Caller holds dev_lock and has set
+   the device. */
+static int fd_txn_ensure( fd_ed25519_gpu_t * g, unsigned long n_txn, unsigned long out_sz ) {
+  hipError_t e;
+  for( int b=0; b<2; b++ ) {
+    fd_txn_set * ts = &g->txn_set[b];
+    if( !ts->done  && (e = hipEventCreateWithFlags( &ts->done, hipEventDisableTiming )) != hipSuccess ) { ts->done = NULL; return fd_gpu_fail( "txn event", e ); }
+    if( !ts->desc  && (e = hipMalloc( (void **)&ts->desc,  g->max_sigs * sizeof(fd_ed25519_gpu_desc_t) )) != hipSuccess ) { ts->desc = NULL; return fd_gpu_fail( "txn scratch", e ); }
+    if( !ts->codes && (e = hipMalloc( (void **)&ts->codes, g->max_sigs * sizeof(int32_t) )) != hipSuccess ) { ts->codes = NULL; return fd_gpu_fail( "txn scratch", e ); }
+  }
+  for( int k=0; k<6; k++ )
+    if( !g->txn_ev[k] && (e = hipEventCreate( &g->txn_ev[k] )) != hipSuccess ) { g->txn_ev[k] = NULL; return fd_gpu_fail( "txn event", e ); }
+  unsigned long cap = g->txn_cap > n_txn ? g->txn_cap : n_txn;
+  unsigned long need = fd_txn_pk_layout( cap, g->max_sigs ).out + out_sz;
+  if( cap == g->txn_cap && need <= g->txn_pk_sz ) return 0;
+  if( (e = hipDeviceSynchronize()) != hipSuccess ) return fd_gpu_fail( "txn scratch (idle)", e );
+  if( cap != g->txn_cap ) {
+    for( int b=0; b<2; b++ ) {
+      fd_txn_set * ts = &g->txn_set[b];
+      if( ts->meta ) hipFree( ts->meta );
+      if( ts->part ) hipFree( ts->part );
+      ts->meta = NULL; ts->part = NULL;
+    }
+    g->txn_cap = 0UL;
+    for( int b=0; b<2; b++ ) {
+      fd_txn_set * ts = &g->txn_set[b];
+      if( (e = hipMalloc( (void **)&ts->meta, cap * sizeof(fd_txn_meta_t) )) != hipSuccess ) { ts->meta = NULL; return fd_gpu_fail( "txn scratch", e ); }
+      if( (e = hipMalloc( (void **)&ts->part, fd_txn_part_cnt( cap ) * sizeof(uint32_t) )) != hipSuccess ) { ts->part = NULL; return fd_gpu_fail( "txn scratch", e ); }
+    }
+  }
+  if( g->d_txn_pk ) hipFree( g->d_txn_pk );
+  if( g->h_txn_pk ) hipHostFree( g->h_txn_pk );
+  g->d_txn_pk = NULL; g->h_txn_pk = NULL; g->txn_pk_sz = 0UL;
+  if( (e = hipMalloc( (void **)&g->d_txn_pk, need )) != hipSuccess ) { g->d_txn_pk = NULL; return fd_gpu_fail( "txn staging", e ); }
+  if( (e = hipHostMalloc( (void **)&g->h_txn_pk, need, hipHostMallocDefault )) != hipSuccess ) { g->h_txn_pk = NULL; return fd_gpu_fail( "txn staging", e ); }
+  g->txn_pk_sz = need;
+  g->txn_cap   = cap;
+  return 0;
+}
+
+extern "C" int fd_ed25519_gpu_txns_reserve( fd_ed25519_gpu_t * g, unsigned long max_txn ) {
+  if( !g || !max_txn || max_txn > FD_TXN_MAX ) return FD_ED25519_ERR_ARG;
+  std::lock_guard<std::mutex> guard( g->dev_lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  return fd_txn_ensure( g, max_txn, 0UL );
+}
+
+static int fd_txn_args_ok( fd_ed25519_gpu_t const * g, unsigned long n_txn, void const * blob, unsigned long blob_sz, void const * txn,
+                           void const * res, void const * txn_out, unsigned long stride ) {
+  if( !g || n_txn > FD_TXN_MAX || blob_sz > 0xffffffffUL || (n_txn && (!txn || !res)) || (blob_sz && !blob) ) return 0;
+  if( (uintptr_t)res & 7UL ) return 0;
+  if( txn_out && ( stride < sizeof(fd_txn_t) || (stride & 1UL) || stride > 65534UL || ((uintptr_t)txn_out & 1UL) ) ) return 0;
+  return 1;
+}
+
+/* The device-resident sequence on `st`, scratch set txn_seq mod 2: wait for
+   the set, parse / scan / expand, the verify pipeline on sig_cap slots
+   (fd_dev_launch orders it after the work on st and st after its codes),
+   reduce.  verify == 0 (fd_ed25519_gpu_debug_txn_descs) stops after expand.
+   ev: NULL or the six timing events.  *set_out: the set used.  Caller
+   holds dev_lock and has called fd_txn_ensure. */
+static int fd_txn_dev_run( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * d_blob, unsigned long blob_sz,
+                           fd_ed25519_gpu_txn_t const * d_txn, unsigned long sig_cap, fd_ed25519_gpu_txn_result_t * d_res,
+                           int * d_codes_opt, void * d_txn_out_opt, unsigned long stride, hipStream_t st, fd_knobs const & kn,
+                           int verify, hipEvent_t const * ev, int * set_out ) {
+  hipError_t e;
+  int b = (int)(g->txn_seq & 1UL);
+  fd_txn_set * ts = &g->txn_set[b];
+  if( set_out ) *set_out = b;
+  if( (e = hipStreamWaitEvent( st, ts->done, 0 )) != hipSuccess ) return fd_gpu_fail( "txn order", e );
+  if( (e = fd_ed25519_gpu_launch_txn_front( n_txn, (uint8_t const *)d_blob, blob_sz, d_txn, sig_cap, d_res, (uint8_t *)d_txn_out_opt,
+                                            d_txn_out_opt ? stride : 0UL, ts->meta, ts->part, ts->desc, st, ev )) != hipSuccess )
+    return fd_gpu_fail( "fd_ed25519_gpu_launch_txn_front", e );
+  if( verify && sig_cap ) {
+    int32_t * codes = d_codes_opt ? (int32_t *)d_codes_opt : ts->codes;
+    int err = fd_dev_launch( g, sig_cap, d_blob, blob_sz, ts->desc, codes, (void *)st, 0, kn );
+    if( err ) return err;
+    if( ev && (e = hipEventRecord( ev[4], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+    if( (e = fd_ed25519_gpu_launch_txn_reduce( n_txn, d_res, codes, st )) != hipSuccess )
+      return fd_gpu_fail( "fd_ed25519_gpu_launch_txn_reduce", e );
+    if( ev && (e = hipEventRecord( ev[5], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+  } else if( ev ) {
+    if( (e = hipEventRecord( ev[4], st )) != hipSuccess || (e = hipEventRecord( ev[5], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+  }
+  if( (e = hipEventRecord( ts->done, st )) != hipSuccess ) return fd_gpu_fail( "txn order", e );
+  g->txn_seq++;
+  return 0;
+}
+
+static int fd_txn_dev_call( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * d_blob, unsigned long blob_sz,
+                            fd_ed25519_gpu_txn_t const * d_txn, unsigned long sig_cap, fd_ed25519_gpu_txn_result_t * d_res,
+                            int * d_codes_opt, void * d_txn_out_opt, unsigned long stride, void * stream, float * kernel_ms ) {
+  if( !fd_txn_args_ok( g, n_txn, d_blob, blob_sz, d_txn, d_res, d_txn_out_opt, stride ) || sig_cap > g->max_sigs || (n_txn && !d_blob) )
+    return FD_ED25519_ERR_ARG;
+  if( kernel_ms ) for( int k=0; k<4; k++ ) kernel_ms[k] = 0.f;
+  if( !n_txn ) return 0;
+  fd_knobs kn = fd_knobs_get( g );     /* before dev_lock: the engine's locks are never nested */
+  std::lock_guard<std::mutex> guard( g->dev_lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  int err = fd_txn_ensure( g, n_txn, 0UL );
+  if( err ) return err;
+  hipStream_t st = stream ? (hipStream_t)stream : g->slot[0].stream;
+  err = fd_txn_dev_run( g, n_txn, d_blob, blob_sz, d_txn, sig_cap, d_res, d_codes_opt, d_txn_out_opt, stride, st, kn, 1,
+                        kernel_ms ? g->txn_ev : NULL, NULL );
+  if( err || !kernel_ms ) return err;
+  if( (err = fd_event_wait( g->txn_ev[5], fd_timeout( g ) )) ) return err;
+  for( int k=0; k<4; k++ )
+    if( (e = hipEventElapsedTime( &kernel_ms[k], g->txn_ev[k == 3 ? 4 : k], g->txn_ev[k == 3 ? 5 : k+1] )) != hipSuccess )
+      return fd_gpu_fail( "elapsed", e );
+  return 0;
+}
+
+extern "C" int fd_ed25519_gpu_verify_txns_dev( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * d_blob, unsigned long blob_sz,
+                                               fd_ed25519_gpu_txn_t const * d_txn, unsigned long sig_cap,
+                                               fd_ed25519_gpu_txn_result_t * d_res, int * d_codes_opt, void * d_txn_out_opt,
+                                               unsigned long txn_out_stride, void * stream ) {
+  return fd_txn_dev_call( g, n_txn, d_blob, blob_sz, d_txn, sig_cap, d_res, d_codes_opt, d_txn_out_opt, txn_out_stride, stream, NULL );
+}
+
+extern "C" int fd_ed25519_gpu_verify_txns_dev_timed( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * d_blob, unsigned long blob_sz,
+                                                     fd_ed25519_gpu_txn_t const * d_txn, unsigned long sig_cap,
+                                                     fd_ed25519_gpu_txn_result_t * d_res, int * d_codes_opt, void * d_txn_out_opt,
+                                                     unsigned long txn_out_stride, void * stream, float * kernel_ms ) {
+  if( !kernel_ms ) return FD_ED25519_ERR_ARG;
+  return fd_txn_dev_call( g, n_txn, d_blob, blob_sz, d_txn, sig_cap, d_res, d_codes_opt, d_txn_out_opt, txn_out_stride, stream, kernel_ms );
+}
+
+/* signatures an entry claims: its first payload byte, if that can be read
+   and is a count fd_txn_parse accepts; an upper bound on what it takes */
+static inline unsigned long fd_txn_claim( uint8_t const * blob, unsigned long blob_sz, fd_ed25519_gpu_txn_t const & e ) {
+  if( !e.sz || (unsigned long)e.off + (unsigned long)e.sz > blob_sz ) return 0UL;
+  unsigned long c = blob[ e.off ];
+  return ( c >= 1UL && c <= FD_TXN_SIG_MAX ) ? c : 0UL;
+}
+
+/* One launch of a host-buffer call on slot sl, whose device blob holds the
+   batch: entries txn[0, nt) in, results, n_sig, codes (verify) or
+   descriptors, and fd_txn_t rows out, all through the staging; waits for
+   it.  Caller holds both engine locks. */
+static int fd_txn_host_run( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long blob_sz, fd_ed25519_gpu_txn_t const * txn,
+                            unsigned long nt, unsigned long cap, unsigned long stride, fd_knobs const & kn, int verify ) {
+  hipError_t e;
+  hipStream_t st = sl->stream;
+  int err = fd_txn_ensure( g, nt, nt * stride );
+  if( err ) return err;
+  fd_txn_pk_off o = fd_txn_pk_layout( g->txn_cap, g->max_sigs );
+  uint8_t * d = g->d_txn_pk, * h = g->h_txn_pk;
+  memcpy( h + o.txn, txn, nt * sizeof(fd_ed25519_gpu_txn_t) );
+  if( (e = hipMemcpyAsync( d + o.txn, h + o.txn, nt * sizeof(fd_ed25519_gpu_txn_t), hipMemcpyHostToDevice, st )) != hipSuccess ) {
+    err = fd_gpu_fail( "H2D transactions", e ); goto drain;
+  }
+  int b;
+  if( (err = fd_txn_dev_run( g, nt, sl->d_blob, blob_sz, (fd_ed25519_gpu_txn_t const *)(d + o.txn), cap,
+                             (fd_ed25519_gpu_txn_result_t *)(d + o.res), NULL, stride ? d + o.out : NULL, stride, st, kn, verify, NULL, &b )) )
+    goto drain;
+  {
+    fd_txn_set * ts = &g->txn_set[b];
+    unsigned long per = verify ? sizeof(int32_t) : sizeof(fd_ed25519_gpu_desc_t);
+    if( (e = hipMemcpyAsync( h + o.res, d + o.res, nt * sizeof(fd_ed25519_gpu_txn_result_t), hipMemcpyDeviceToHost, st )) != hipSuccess
+     || (e = hipMemcpyAsync( h + o.nsig, ts->part + fd_txn_part_cnt( nt ) - 1UL, sizeof(uint32_t), hipMemcpyDeviceToHost, st )) != hipSuccess
+     || ( cap && (e = hipMemcpyAsync( h + o.sig, verify ? (void const *)ts->codes : (void const *)ts->desc, cap * per, hipMemcpyDeviceToHost, st )) != hipSuccess )
+     || ( stride && (e = hipMemcpyAsync( h + o.out, d + o.out, nt * stride, hipMemcpyDeviceToHost, st )) != hipSuccess )
+     || (e = hipEventRecord( sl->done, st )) != hipSuccess ) { err = fd_gpu_fail( "D2H transactions", e ); goto drain; }
+  }
+  err = fd_event_wait( sl->done, fd_timeout( g ) );
+  if( err ) { sl->ticket = g->next_ticket++; sl->orphan = 1; }
+  return err;
+drain:
+  (void)hipStreamSynchronize( st );
+  (void)hipGetLastError();
+  return err;
+}
+
+/* the batch's bytes into slot sl's device blob (with the pad the kernels
+   may read past blob_sz) */
+static int fd_txn_blob_in( fd_ed25519_gpu_slot * sl, void const * blob, unsigned long blob_sz ) {
+  if( blob_sz ) memcpy( sl->h_blob, blob, blob_sz );
+  memset( sl->h_blob + blob_sz, 0, FD_BLOB_PAD );
+  hipError_t e = hipMemcpyAsync( sl->d_blob, sl->h_blob, blob_sz + FD_BLOB_PAD, hipMemcpyHostToDevice, sl->stream );
+  if( e != hipSuccess ) { (void)hipStreamSynchronize( sl->stream ); return fd_gpu_fail( "H2D transaction blob", e ); }
+  return 0;
+}
+
+extern "C" int fd_ed25519_gpu_verify_txns_packed( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
+                                                  fd_ed25519_gpu_txn_t const * txn, fd_ed25519_gpu_txn_result_t * res, int * codes_opt,
+                                                  void * txn_out_opt, unsigned long txn_out_stride ) {
+  if( !g || blob_sz > g->max_blob ) return FD_ED25519_ERR_ARG;
+  /* results are staged, so the caller's res needs no alignment */
+  if( !fd_txn_args_ok( g, 0UL, blob, blob_sz, txn, NULL, txn_out_opt, txn_out_stride ) || (n_txn && (!txn || !res)) )
+    return FD_ED25519_ERR_ARG;
+  if( !n_txn ) return 0;
+  unsigned long stride = txn_out_opt ? txn_out_stride : 0UL;
+  fd_knobs kn = fd_knobs_get( g );
+  /* both engine locks, dev_lock first, as fd_ed25519_gpu_debug_k */
+  std::lock_guard<std::mutex> dguard( g->dev_lock );
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
+  if( !sl ) return FD_ED25519_ERR_ARG;
+  int err = fd_txn_blob_in( sl, blob, blob_sz );
+  if( err ) return err;
+  /* nothing is written on failure: everything lands in these first */
+  std::vector<fd_ed25519_gpu_txn_result_t> hres( n_txn );
+  std::vector<int32_t> hcodes;
+  std::vector<uint8_t> hout( stride ? n_txn * stride : 0UL );
+  unsigned long sig_total = 0UL, i = 0UL;
+  while( i < n_txn ) {
+    /* the longest run of transactions claiming at most max_sigs signatures */
+    unsigned long j = i, claimed = 0UL;
+    while( j < n_txn && j - i < FD_TXN_MAX ) {
+      unsigned long c = fd_txn_claim( (uint8_t const *)blob, blob_sz, txn[j] );
+      if( j > i && claimed + c > g->max_sigs ) break;
+      claimed += c; j++;
+    }
+    unsigned long nt = j - i, cap = claimed < g->max_sigs ? claimed : g->max_sigs;
+    if( (err = fd_txn_host_run( g, sl, blob_sz, txn + i, nt, cap, stride, kn, 1 )) ) return err;
+    fd_txn_pk_off o = fd_txn_pk_layout( g->txn_cap, g->max_sigs );
+    uint8_t const * h = g->h_txn_pk;
+    unsigned long n_sig = *(uint32_t const *)(h + o.nsig);
+    if( n_sig > cap ) { snprintf( fd_gpu_err, sizeof(fd_gpu_err), "verify_txns: %lu slots taken of %lu", n_sig, cap ); return FD_ED25519_ERR_GPU; }
+    memcpy( &hres[i], h + o.res, nt * sizeof(fd_ed25519_gpu_txn_result_t) );
+    for( unsigned long t=i; t<j; t++ ) hres[t].sig_base += (uint32_t)sig_total;
+    if( codes_opt ) hcodes.insert( hcodes.end(), (int32_t const *)(h + o.sig), (int32_t const *)(h + o.sig) + n_sig );
+    if( stride ) memcpy( &hout[i * stride], h + o.out, nt * stride );
+    sig_total += n_sig;
+    i = j;
+  }
+  memcpy( res, hres.data(), n_txn * sizeof(fd_ed25519_gpu_txn_result_t) );
+  if( codes_opt && sig_total ) memcpy( codes_opt, hcodes.data(), sig_total * sizeof(int32_t) );
+  if( stride )
+    for( unsigned long t=0; t<n_txn; t++ ) {
+      unsigned long fp = hres[t].footprint;
+      if( fp && fp <= stride ) memcpy( (uint8_t *)txn_out_opt + t * stride, &hout[t * stride], fp );
+    }
+  return 0;
+}
+
+extern "C" int fd_ed25519_gpu_debug_txn_descs( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
+                                               fd_ed25519_gpu_txn_t const * txn, unsigned long sig_cap, fd_ed25519_gpu_desc_t * desc_out,
+                                               unsigned long * n_sig_out, fd_ed25519_gpu_txn_result_t * res_opt ) {
+  if( !g || !n_txn || n_txn > FD_TXN_MAX || blob_sz > g->max_blob || sig_cap > g->max_sigs || !txn || !n_sig_out || (sig_cap && !desc_out)
+      || (blob_sz && !blob) ) return FD_ED25519_ERR_ARG;
+  fd_knobs kn = fd_knobs_get( g );
+  std::lock_guard<std::mutex> dguard( g->dev_lock );
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
+  if( !sl ) return FD_ED25519_ERR_ARG;
+  int err = fd_txn_blob_in( sl, blob, blob_sz );
+  if( err ) return err;
+  if( (err = fd_txn_host_run( g, sl, blob_sz, txn, n_txn, sig_cap, 0UL, kn, 0 )) ) return err;
+  fd_txn_pk_off o = fd_txn_pk_layout( g->txn_cap, g->max_sigs );
+  uint8_t const * h = g->h_txn_pk;
+  *n_sig_out = *(uint32_t const *)(h + o.nsig);
+  if( sig_cap ) memcpy( desc_out, h + o.sig, sig_cap * sizeof(fd_ed25519_gpu_desc_t) );
+  if( res_opt ) memcpy( res_opt, h + o.res, n_txn * sizeof(fd_ed25519_gpu_txn_result_t) );
+  return 0;
 }

@@ -12,6 +12,8 @@ fd_txn_t byte layout (src/ballet/txn/fd_txn.h:107-320).
                          (src/ballet/txn/fd_txn.h:159-217)
   frag(payload)       -> the QUIC tile's frag: payload | pad to 2 | fd_txn_t |
                          u16 payload_sz (src/disco/quic/fd_quic_tile.c:475-516)
+  pack(payloads)      -> (blob, txns): the payloads laid out in one blob for
+                         Engine.verify_txns (fd_ed25519_gpu_txn.h)
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ import struct
 
 import numpy as np
 
-from . import DESC_DTYPE, lib
+from . import DESC_DTYPE, TXN_DTYPE, lib
 
 TXN_MTU = 1232            # FD_TPU_MTU
 SIG_MAX = 127             # FD_TXN_SIG_MAX, src/ballet/txn/fd_txn.h:65
@@ -92,3 +94,19 @@ def frag(payload: bytes):
         return None
     pad = b"\x00" * (len(payload) & 1)
     return bytes(payload) + pad + raw + struct.pack("<H", len(payload))
+
+
+def pack(payloads, gap: int = 0, first: int = 0, pad: int = 64):
+    """(blob, txns) for Engine.verify_txns: payload t at blob[txns[t].off ..+txns[t].sz),
+    the first at offset `first`, `gap` unused bytes between neighbours (any
+    alignment is fine: the device reads payload bytes one by one), `pad` zero
+    bytes at the end."""
+    txns = np.zeros(len(payloads), TXN_DTYPE)
+    off = first
+    for t, p in enumerate(payloads):
+        txns[t] = (off, len(p))
+        off += len(p) + gap
+    blob = np.zeros(off + pad, np.uint8)
+    for t, p in enumerate(payloads):
+        blob[txns[t]["off"]:txns[t]["off"] + len(p)] = np.frombuffer(bytes(p), np.uint8)
+    return blob, txns

@@ -1,0 +1,162 @@
+/* txn_core_harness.cpp -- the parser core (firedancer_amd/csrc/fd_txn_core.h,
+   the code fd_k_txn_parse runs one lane per transaction) compiled for the
+   host, for tests/test_txn_core_host.py (as a shared object) and
+   tests/test_txn_core_sanitize.py (with its own main, -DTXN_HARNESS_MAIN,
+   under AddressSanitizer and UndefinedBehaviorSanitizer).
+
+   Every payload is parsed from the END of a heap block of exactly its
+   size, so a read one byte past payload[0, payload_sz) leaves the block. */
+
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "fd_txn_core.h"
+
+typedef unsigned long (*parser_fn)( uint8_t const *, unsigned long, void *, fd_txn_parse_counters_t * );
+
+#define OUT_SZ (1UL<<19)    /* any descriptor of a payload <= 65535 bytes: 20 + 10*21845 */
+
+static uint8_t * exact_copy( uint8_t const * p, unsigned long sz ) {
+  uint8_t * b = (uint8_t *)malloc( sz ? sz : 1UL );
+  if( !b ) abort();
+  if( sz ) memcpy( b, p, sz );
+  return b;
+}
+
+/* field by field: the struct has padding */
+static int sum_ne( fd_txn_core_sum_t const * a, fd_txn_core_sum_t const * b ) {
+  return a->tag != b->tag || a->footprint != b->footprint || a->reject_line != b->reject_line || a->acct_addr_off != b->acct_addr_off
+      || a->sig_cnt != b->sig_cnt || a->version != b->version;
+}
+
+extern "C" {
+
+/* fd_txn_parse built from the core here: same signature, same counters */
+unsigned long
+core_txn_parse( uint8_t const * payload, unsigned long sz, void * out, fd_txn_parse_counters_t * ctr ) {
+  uint8_t * b = exact_copy( payload, sz );
+  fd_txn_core_sum_t sum;
+  unsigned long fp = fd_txn_core_parse( b, sz, out, FD_TXN_CORE_CAP_TRUSTED, &sum );
+  free( b );
+  if( ctr ) {
+    if( fp ) ctr->success_cnt++;
+    else     ctr->failure_ring[ (ctr->failure_cnt++) % FD_TXN_PARSE_COUNTERS_RING_SZ ] = (unsigned long)sum.reject_line;
+  }
+  return fp;
+}
+
+/* the summary alone (no descriptor buffer): {tag, footprint, reject_line,
+   acct_addr_off, sig_cnt, version} as six unsigned longs */
+unsigned long
+core_txn_summary( uint8_t const * payload, unsigned long sz, unsigned long * f ) {
+  uint8_t * b = exact_copy( payload, sz );
+  fd_txn_core_sum_t sum;
+  unsigned long fp = fd_txn_core_parse( b, sz, NULL, 0UL, &sum );
+  free( b );
+  f[0] = sum.tag; f[1] = sum.footprint; f[2] = sum.reject_line; f[3] = sum.acct_addr_off; f[4] = sum.sig_cnt; f[5] = sum.version;
+  return fp;
+}
+
+/* One payload through the core in all its modes against another parser
+   with fd_txn_parse's signature (NULL: the core's own trusted single walk).
+   Returns 0 if everything agrees, else the number of the first check that
+   does not. */
+int
+core_txn_cmp( uint8_t const * payload, unsigned long sz, parser_fn other ) {
+  static uint8_t * o_ref, * o_core;
+  if( !o_ref ) { o_ref = (uint8_t *)malloc( OUT_SZ ); o_core = (uint8_t *)malloc( OUT_SZ ); if( !o_ref || !o_core ) abort(); }
+  fd_txn_parse_counters_t ctr;
+  memset( &ctr, 0, sizeof(ctr) );
+  unsigned long r = other ? other( payload, sz, o_ref, &ctr ) : core_txn_parse( payload, sz, o_ref, &ctr );
+  uint8_t * b = exact_copy( payload, sz );
+  int bad = 0;
+  fd_txn_core_sum_t s0, s1, s2;
+  /* no buffer */
+  unsigned long r0 = fd_txn_core_parse( b, sz, NULL, 0UL, &s0 );
+  /* a buffer exactly its footprint (or, rejected, of any size): written */
+  memset( o_core, 0xA5, ( r > 20UL ? r : 20UL ) + 1UL );
+  unsigned long r1 = fd_txn_core_parse( b, sz, o_core, r ? r : OUT_SZ, &s1 );
+  if( r0 != r || r1 != r ) bad = 1;
+  else if( r && memcmp( o_core, o_ref, r ) ) bad = 2;
+  else if( r && o_core[ r ] != 0xA5 ) bad = 3;                      /* not a byte past the footprint */
+  else if( !r && ( o_core[0] != 0xA5 || o_core[19] != 0xA5 ) ) bad = 4;   /* a rejected payload writes nothing here */
+  else if( sum_ne( &s0, &s1 ) ) bad = 5;
+  else if( s0.footprint != r ) bad = 6;
+  else if( r ) {
+    fd_txn_t const * t = (fd_txn_t const *)o_ref;
+    uint64_t tag = 0;
+    for( int k=7; k>=0; k-- ) tag = (tag << 8) | payload[ t->signature_off + k ];
+    if( s0.reject_line || ctr.success_cnt != 1 ) bad = 7;
+    else if( s0.sig_cnt != t->signature_cnt || s0.version != t->transaction_version || s0.acct_addr_off != t->acct_addr_off ) bad = 8;
+    else if( s0.tag != tag ) bad = 9;
+    else {
+      /* one byte short of its footprint: not a byte written */
+      memset( o_core, 0xA5, r );
+      unsigned long r2 = fd_txn_core_parse( b, sz, o_core, r - 1UL, &s2 );
+      if( r2 != r || sum_ne( &s2, &s0 ) ) bad = 10;
+      else for( unsigned long k=0; k<r; k++ ) if( o_core[ k ] != 0xA5 ) { bad = 11; break; }
+    }
+  } else {
+    if( ctr.failure_cnt != 1 || s0.reject_line != ctr.failure_ring[0] || !s0.reject_line ) bad = 12;
+    else if( s0.sig_cnt || s0.tag || s0.acct_addr_off || s0.version != FD_TXN_VLEGACY ) bad = 13;
+  }
+  free( b );
+  return bad;
+}
+
+/* test_mutate's input set (every truncation, every other value of every
+   byte) through core_txn_cmp.  Returns the number of payloads that
+   disagree; *first = {position, value or -1 for the truncation, check}. */
+unsigned long
+core_txn_sweep_cmp( uint8_t const * payload, unsigned long n, parser_fn other, long * first ) {
+  uint8_t * buf = (uint8_t *)malloc( n ? n : 1UL );
+  if( !buf ) abort();
+  memcpy( buf, payload, n );
+  unsigned long nbad = 0;
+  for( unsigned long i=0; i<=n; i++ ) {
+    int bad = core_txn_cmp( buf, i, other );
+    if( bad && !nbad++ && first ) { first[0] = (long)i; first[1] = -1L; first[2] = bad; }
+    if( i == n ) break;
+    uint8_t orig = buf[ i ];
+    for( int d=1; d<256; d++ ) {
+      buf[ i ] = (uint8_t)( orig + d );
+      bad = core_txn_cmp( buf, n, other );
+      if( bad && !nbad++ && first ) { first[0] = (long)i; first[1] = buf[ i ]; first[2] = bad; }
+    }
+    buf[ i ] = orig;
+  }
+  free( buf );
+  return nbad;
+}
+
+}
+
+#ifdef TXN_HARNESS_MAIN
+/* argv: fixture files.  The sweep of each through every mode of the core,
+   then a few synthetic shapes (empty, oversized, deep compact-u16s). */
+int main( int argc, char ** argv ) {
+  unsigned long swept = 0;
+  for( int a=1; a<argc; a++ ) {
+    FILE * f = fopen( argv[a], "rb" );
+    if( !f ) { printf( "cannot open %s\n", argv[a] ); return 2; }
+    static uint8_t p[ 1<<16 ];
+    unsigned long n = fread( p, 1, sizeof(p), f );
+    fclose( f );
+    fd_txn_core_sum_t sum;
+    if( core_txn_cmp( p, n, NULL ) || !fd_txn_core_parse( p, n, NULL, 0UL, &sum ) ) { printf( "%s does not parse\n", argv[a] ); return 1; }
+    long first[3] = { 0, 0, 0 };
+    unsigned long nbad = core_txn_sweep_cmp( p, n, NULL, first );
+    if( nbad ) { printf( "%s: %lu payloads disagree, first at %ld value %ld check %ld\n", argv[a], nbad, first[0], first[1], first[2] ); return 1; }
+    swept += n * 256UL + 1UL;
+  }
+  static uint8_t big[ 70001 ];
+  big[0] = 1;
+  if( core_txn_cmp( big, 0, NULL ) || core_txn_cmp( big, 1, NULL ) || core_txn_cmp( big, 65535, NULL ) || core_txn_cmp( big, 65536, NULL )
+      || core_txn_cmp( big, 70001, NULL ) ) { printf( "synthetic shapes disagree\n" ); return 1; }
+  memset( big, 0x80, 300 );
+  for( unsigned long sz=0; sz<300; sz++ ) if( core_txn_cmp( big, sz, NULL ) ) { printf( "0x80 run disagrees at %lu\n", sz ); return 1; }
+  printf( "%lu payloads ok\n", swept );
+  return 0;
+}
+#endif
