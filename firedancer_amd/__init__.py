@@ -273,6 +273,18 @@ def lib() -> ctypes.CDLL:
         L.fd_ed25519_gpu_verify_txns_packed.restype = ip
         L.fd_ed25519_gpu_debug_txn_descs.argtypes = [vp, ul, vp, ul, vp, ul, vp, ctypes.POINTER(ul), vp]
         L.fd_ed25519_gpu_debug_txn_descs.restype = ip
+        L.fd_ed25519_gpu_txn_claims.argtypes = [vp, ul, vp, ul, vp]
+        L.fd_ed25519_gpu_txn_claims.restype = ul
+        L.fd_ed25519_gpu_try_submit_txns.argtypes = [vp, ul, vp, ul, vp, ctypes.POINTER(ul)]
+        L.fd_ed25519_gpu_try_submit_txns.restype = ip
+        L.fd_ed25519_gpu_submit_txns.argtypes = [vp, ul, vp, ul, vp, ctypes.POINTER(ul)]
+        L.fd_ed25519_gpu_submit_txns.restype = ip
+        L.fd_ed25519_gpu_poll_txns.argtypes = [vp, ul, vp, vp, ip]
+        L.fd_ed25519_gpu_poll_txns.restype = ip
+        L.fd_ed25519_gpu_txn_ring_allocs.argtypes = [vp]
+        L.fd_ed25519_gpu_txn_ring_allocs.restype = ul
+        L.fd_ed25519_gpu_txn_ring_timed.argtypes = [vp, ul, vp, ul, vp, vp, vp]
+        L.fd_ed25519_gpu_txn_ring_timed.restype = ip
         _lib = L
     return _lib
 
@@ -301,6 +313,7 @@ class Engine:
         self.max_sigs = max_sigs
         self.max_blob = max_blob
         self._pending = {}
+        self._pending_txns = {}     # ticket -> n_sig (the claimed total)
         self._registered = []
 
     def close(self):
@@ -574,6 +587,63 @@ class Engine:
             raise EngineError(f"verify_txns_dev: {strerror(err)}: {last_error()}")
         return ms
 
+    def try_submit_txns(self, blob: np.ndarray, txns: np.ndarray):
+        """Queue a batch of whole transactions on the pinned ring
+        (fd_ed25519_gpu_try_submit_txns) -> its ticket, or None when the ring is full."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=TXN_DTYPE)
+        t = ctypes.c_ulong(0)
+        r = lib().fd_ed25519_gpu_try_submit_txns(self._h, len(txns), _p(blob), blob.nbytes, _p(txns), ctypes.byref(t))
+        if r < 0:
+            raise EngineError(f"try_submit_txns: {strerror(r)}: {last_error()}")
+        if r == 0:
+            return None
+        self._pending_txns[t.value] = int(lib().fd_ed25519_gpu_txn_claims(_p(blob), blob.nbytes, _p(txns), len(txns), None))
+        return t.value
+
+    def submit_txns(self, blob: np.ndarray, txns: np.ndarray) -> int:
+        """try_submit_txns, raising on a full ring as submit does."""
+        t = self.try_submit_txns(blob, txns)
+        if t is None:
+            raise EngineError(f"submit_txns: {strerror(ERR_ARG)}: the ring is full")
+        return t
+
+    def poll_txns(self, ticket: int, n_txn: int, want_codes: bool = False, block: bool = True):
+        """Collect a transaction ticket (fd_ed25519_gpu_poll_txns) -> its n_txn results
+        (TXN_RESULT_DTYPE; sig_base is the prefix of the claims, txn_claims), or
+        (results, codes) with the per-signature codes by claimed slot when want_codes;
+        None while the batch is in flight (block=False)."""
+        n_sig = self._pending_txns.get(ticket)
+        if n_sig is None:
+            raise EngineError(f"poll_txns: unknown ticket {ticket}")
+        res = np.zeros(int(n_txn), TXN_RESULT_DTYPE)
+        codes = np.zeros(max(n_sig, 1), np.int32) if want_codes else None
+        r = lib().fd_ed25519_gpu_poll_txns(self._h, ticket, _p(res), _p(codes) if want_codes else None, 1 if block else 0)
+        if r < 0:
+            raise EngineError(f"poll_txns: {strerror(r)}: {last_error()}")
+        if r == 0:
+            return None
+        del self._pending_txns[ticket]
+        return (res, codes[:n_sig]) if want_codes else res
+
+    def txn_ring_allocs(self) -> int:
+        """Diagnostics: ring slots whose transaction scratch has been allocated."""
+        return int(lib().fd_ed25519_gpu_txn_ring_allocs(self._h))
+
+    TXN_RING_KERNELS = ("fd_k_txn_ring_front", "fd_k_txn_ring_reduce")
+
+    def txn_ring_timed(self, blob: np.ndarray, txns: np.ndarray):
+        """Diagnostics (fd_ed25519_gpu_txn_ring_timed): one ring batch, submitted and
+        polled -> (results, the two ring kernels' durations in ms, TXN_RING_KERNELS order)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=TXN_DTYPE)
+        res = np.zeros(len(txns), TXN_RESULT_DTYPE)
+        ms = np.zeros(2, np.float32)
+        err = lib().fd_ed25519_gpu_txn_ring_timed(self._h, len(txns), _p(blob), blob.nbytes, _p(txns), _p(res), _p(ms))
+        if err:
+            raise EngineError(f"txn_ring_timed: {strerror(err)}: {last_error()}")
+        return res, ms
+
     TXN_KERNELS = ("fd_k_txn_parse", "fd_k_txn_scan", "fd_k_txn_expand", "fd_k_txn_reduce")
 
     def debug_txn_descs(self, blob: np.ndarray, txns: np.ndarray, sig_cap: int):
@@ -836,6 +906,16 @@ def verify_batch_single_msg(msg: bytes, sigs: np.ndarray, pubs: np.ndarray) -> t
     out = np.zeros(n, dtype=np.int32)
     r = lib().fd_ed25519_verify_batch_single_msg(m, len(msg), _p(sigs), _p(pubs), n, _p(out))
     return r, out
+
+
+def txn_claims(blob: np.ndarray, txns: np.ndarray):
+    """fd_ed25519_gpu_txn_claims -> (bases[n_txn + 1] uint32, n_sig): the slots a ring
+    batch's transactions claim by their first payload byte, as an exclusive prefix."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    txns = np.ascontiguousarray(txns, dtype=TXN_DTYPE)
+    bases = np.zeros(len(txns) + 1, np.uint32)
+    n_sig = lib().fd_ed25519_gpu_txn_claims(_p(blob), blob.nbytes, _p(txns), len(txns), _p(bases))
+    return bases, int(n_sig)
 
 
 def device_count() -> int:

@@ -29,6 +29,7 @@
 #include "fd_ed25519_gpu_diag.h"
 #include "fd_ed25519_gpu_sign_private.h"
 #include "fd_ed25519_gpu_txn_private.h"
+#include "fd_ed25519_gpu_txn_claim.h"
 
 #define FD_GPU_DEPTH_DEFAULT 3
 #define FD_GPU_DEPTH_MAX     8
@@ -169,6 +170,13 @@ struct fd_ed25519_gpu_slot {
   int                     retiring; /* its codes were taken early: reclaimed once its event completes */
   uint8_t *               h_dig;    /* pinned digests (SHA-512 batch), allocated on first use */
   uint8_t *               h_sgn;    /* pinned signing results (100 B per signature), allocated on first use */
+  /* transaction batches on the ring (fd_ed25519_gpu_submit_txns): the
+     slot's own scratch, allocated by fd_txn_ring_ensure */
+  unsigned long                 n_txn;     /* transactions of the batch in flight; 0: a descriptor batch */
+  fd_ed25519_gpu_desc_t *       t_desc;    /* device: max_sigs descriptors, written by fd_k_txn_ring_front */
+  fd_ed25519_gpu_txn_result_t * t_res;     /* device: max_sigs results, between front and reduce */
+  fd_ed25519_gpu_txn_result_t * h_res;     /* pinned, mapped, coherent: the final results */
+  fd_ed25519_gpu_txn_result_t * h_res_dev; /* h_res as the device addresses it */
 };
 
 /* one of the two scratch sets of the transaction calls (fd_ed25519_gpu_txn.h) */
@@ -227,6 +235,9 @@ struct fd_ed25519_gpu {
   uint8_t *     h_txn_pk;         /* pinned, the same layout */
   unsigned long txn_pk_sz;
   hipEvent_t    txn_ev[6];        /* per-kernel timing events of the transaction kernels */
+  /* transaction batches on the ring (under the ring lock) */
+  unsigned long txn_ring_allocs;  /* slots whose transaction scratch was allocated (fd_ed25519_gpu_txn_ring_allocs) */
+  hipEvent_t    txn_ring_ev[4];   /* fd_ed25519_gpu_txn_ring_timed: around the front kernel and the reduce */
   fd_ring_lock  lock;
 };
 
@@ -468,6 +479,9 @@ extern "C" void fd_ed25519_gpu_delete( fd_ed25519_gpu_t * g ) {
     if( sl->h_out  ) hipHostFree( sl->h_out );
     if( sl->h_dig  ) hipHostFree( sl->h_dig );
     if( sl->h_sgn  ) hipHostFree( sl->h_sgn );
+    if( sl->h_res  ) hipHostFree( sl->h_res );
+    if( sl->t_desc ) hipFree( sl->t_desc );
+    if( sl->t_res  ) hipFree( sl->t_res );
     if( sl->d_blob ) hipFree( sl->d_blob );
     if( sl->d_desc ) hipFree( sl->d_desc );
     if( sl->d_out  ) hipFree( sl->d_out );
@@ -497,6 +511,7 @@ extern "C" void fd_ed25519_gpu_delete( fd_ed25519_gpu_t * g ) {
   if( g->d_txn_pk ) hipFree( g->d_txn_pk );
   if( g->h_txn_pk ) hipHostFree( g->h_txn_pk );
   for( int k=0; k<6; k++ ) if( g->txn_ev[k] ) hipEventDestroy( g->txn_ev[k] );
+  for( int k=0; k<4; k++ ) if( g->txn_ring_ev[k] ) hipEventDestroy( g->txn_ring_ev[k] );
   delete g;
 }
 
@@ -644,7 +659,7 @@ static void fd_reclaim_orphans( fd_ed25519_gpu_t * g ) {
       /* an orphan is nobody's: its stage (if the failing caller has not
          unstaged it yet) goes with it; a retiring slot keeps its owner's */
       if( sl->orphan ) sl->staged = 0;
-      sl->orphan = 0; sl->retiring = 0; sl->ticket = 0;
+      sl->orphan = 0; sl->retiring = 0; sl->ticket = 0; sl->n_txn = 0UL;
     }
   }
 }
@@ -980,7 +995,7 @@ static int fd_slot_enqueue_( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, uns
   if( !odirect && (e = hipMemcpyAsync( sl->h_out, sl->d_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st )) != hipSuccess )
     return fd_gpu_fail( "D2H out", e );
   if( (e = hipEventRecord( sl->done, st )) != hipSuccess ) return fd_gpu_fail( "event", e );
-  sl->n = n;
+  sl->n = n; sl->n_txn = 0UL;
   return 0;
 }
 
@@ -1088,6 +1103,9 @@ extern "C" int fd_ed25519_gpu_poll( fd_ed25519_gpu_t * g, unsigned long ticket, 
   {
     std::lock_guard<fd_ring_lock> guard( g->lock );
     for( int s=0; s<g->depth && !sl; s++ ) if( g->slot[s].ticket == ticket ) sl = &g->slot[s];
+    /* a transaction ticket's results are fd_ed25519_gpu_poll_txns's; a
+       drain (out NULL) takes either kind.  The ticket stays valid */
+    if( sl && sl->n_txn && out ) return FD_ED25519_ERR_ARG;
   }
   if( !sl ) return FD_ED25519_ERR_ARG;
   if( (block & 1) && sl->early && out ) {   /* a drain (out NULL) waits for the event */
@@ -1116,7 +1134,7 @@ extern "C" int fd_ed25519_gpu_poll( fd_ed25519_gpu_t * g, unsigned long ticket, 
   }
   std::lock_guard<fd_ring_lock> guard( g->lock );
   if( out ) fd_slot_collect( sl, out );
-  sl->ticket = 0; sl->early = 0;
+  sl->ticket = 0; sl->early = 0; sl->n_txn = 0UL;
   if( block & FD_ED25519_GPU_POLL_KEEP ) sl->staged = 1;   /* lent back to the caller (unstage to free) */
   return 1;
 }
@@ -1969,12 +1987,36 @@ static int fd_txn_ensure( fd_ed25519_gpu_t * g, unsigned long n_txn, unsigned lo
   return 0;
 }
 
+/* The ring slots' own transaction scratch (descriptors, results between
+   the kernels, the pinned results the host reads): every slot that has
+   none yet gets it, so two batches in flight share nothing.  Caller holds
+   the ring lock and has set the device. */
+static int fd_txn_ring_ensure( fd_ed25519_gpu_t * g ) {
+  hipError_t e;
+  for( int s=0; s<g->depth; s++ ) {
+    fd_ed25519_gpu_slot * sl = &g->slot[s];
+    if( sl->t_desc && sl->t_res && sl->h_res_dev ) continue;
+    if( !sl->t_desc && (e = hipMalloc( (void **)&sl->t_desc, g->max_sigs * sizeof(fd_ed25519_gpu_desc_t) )) != hipSuccess ) { sl->t_desc = NULL; return fd_gpu_fail( "txn ring scratch", e ); }
+    if( !sl->t_res  && (e = hipMalloc( (void **)&sl->t_res,  g->max_sigs * sizeof(fd_ed25519_gpu_txn_result_t) )) != hipSuccess ) { sl->t_res = NULL; return fd_gpu_fail( "txn ring scratch", e ); }
+    if( !sl->h_res  && (e = hipHostMalloc( (void **)&sl->h_res, g->max_sigs * sizeof(fd_ed25519_gpu_txn_result_t),
+                                           hipHostMallocMapped | hipHostMallocCoherent )) != hipSuccess ) { sl->h_res = NULL; return fd_gpu_fail( "txn ring results", e ); }
+    if( (e = hipHostGetDevicePointer( (void **)&sl->h_res_dev, sl->h_res, 0 )) != hipSuccess ) { sl->h_res_dev = NULL; return fd_gpu_fail( "txn ring results (mapped)", e ); }
+    g->txn_ring_allocs++;
+  }
+  return 0;
+}
+
 extern "C" int fd_ed25519_gpu_txns_reserve( fd_ed25519_gpu_t * g, unsigned long max_txn ) {
   if( !g || !max_txn || max_txn > FD_TXN_MAX ) return FD_ED25519_ERR_ARG;
   std::lock_guard<std::mutex> guard( g->dev_lock );
   hipError_t e = hipSetDevice( g->device );
   if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  return fd_txn_ensure( g, max_txn, 0UL );
+  int err = fd_txn_ensure( g, max_txn, 0UL );
+  if( err ) return err;
+  /* the ring's slots too (dev_lock, then the ring lock, as
+     fd_ed25519_gpu_verify_txns_packed orders them) */
+  std::lock_guard<fd_ring_lock> rguard( g->lock );
+  return fd_txn_ring_ensure( g );
 }
 
 static int fd_txn_args_ok( fd_ed25519_gpu_t const * g, unsigned long n_txn, void const * blob, unsigned long blob_sz, void const * txn,
@@ -2058,14 +2100,6 @@ extern "C" int fd_ed25519_gpu_verify_txns_dev_timed( fd_ed25519_gpu_t * g, unsig
   return fd_txn_dev_call( g, n_txn, d_blob, blob_sz, d_txn, sig_cap, d_res, d_codes_opt, d_txn_out_opt, txn_out_stride, stream, kernel_ms );
 }
 
-/* signatures an entry claims: its first payload byte, if that can be read
-   and is a count fd_txn_parse accepts; an upper bound on what it takes */
-static inline unsigned long fd_txn_claim( uint8_t const * blob, unsigned long blob_sz, fd_ed25519_gpu_txn_t const & e ) {
-  if( !e.sz || (unsigned long)e.off + (unsigned long)e.sz > blob_sz ) return 0UL;
-  unsigned long c = blob[ e.off ];
-  return ( c >= 1UL && c <= FD_TXN_SIG_MAX ) ? c : 0UL;
-}
-
 /* One launch of a host-buffer call on slot sl, whose device blob holds the
    batch: entries txn[0, nt) in, results, n_sig, codes (verify) or
    descriptors, and fd_txn_t rows out, all through the staging; waits for
@@ -2142,7 +2176,7 @@ extern "C" int fd_ed25519_gpu_verify_txns_packed( fd_ed25519_gpu_t * g, unsigned
     /* the longest run of transactions claiming at most max_sigs signatures */
     unsigned long j = i, claimed = 0UL;
     while( j < n_txn && j - i < FD_TXN_MAX ) {
-      unsigned long c = fd_txn_claim( (uint8_t const *)blob, blob_sz, txn[j] );
+      unsigned long c = fd_txn_claim( (uint8_t const *)blob, blob_sz, &txn[j] );
       if( j > i && claimed + c > g->max_sigs ) break;
       claimed += c; j++;
     }
@@ -2189,5 +2223,196 @@ extern "C" int fd_ed25519_gpu_debug_txn_descs( fd_ed25519_gpu_t * g, unsigned lo
   *n_sig_out = *(uint32_t const *)(h + o.nsig);
   if( sig_cap ) memcpy( desc_out, h + o.sig, sig_cap * sizeof(fd_ed25519_gpu_desc_t) );
   if( res_opt ) memcpy( res_opt, h + o.res, n_txn * sizeof(fd_ed25519_gpu_txn_result_t) );
+  return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* Transactions through the ring (fd_ed25519_gpu_submit_txns). */
+
+/* fd_slot_enqueue_ for a transaction batch: the blob reaches the slot's
+   device buffer as a descriptor batch's does (DMA from a registered
+   region, the slot's own staged h_blob as it lies, anything else staged),
+   and the batch's entries and claim prefix travel in the descriptors'
+   place: packed 16-aligned behind the staged blob in the one H2D copy, or,
+   beside a registered blob, in the slot's mapped descriptor buffer, which
+   the front kernel reads over the link (12 bytes per transaction).  Then
+   fd_k_txn_ring_front, the ring's verify launch on the slot's work area
+   with the slot's transaction descriptors, and fd_k_txn_ring_reduce, which
+   leaves the results in the slot's mapped pinned h_res.  ev: NULL, or four
+   events around the front kernel and the reduce. */
+static int fd_txn_slot_enqueue_( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n_txn, void const * blob,
+                                 unsigned long blob_sz, fd_ed25519_gpu_txn_t const * txn, hipStream_t * used, hipEvent_t const * ev ) {
+  unsigned long doff    = fd_desc_off( blob_sz );
+  unsigned long txn_sz  = n_txn * sizeof(fd_ed25519_gpu_txn_t);
+  unsigned long tail_sz = txn_sz + ( n_txn + 1UL ) * sizeof(uint32_t);   /* <= 16 n_txn <= the descriptors' room */
+  int direct = sl->h_blob != blob && blob_sz && fd_registered( g, blob, blob_sz );
+  int const zc = direct && sl->h_desc_dev;
+  uint8_t * tail = direct ? (uint8_t *)sl->h_desc : sl->h_blob + doff;
+  if( !direct ) {
+    if( sl->h_blob != blob && blob_sz ) memcpy( sl->h_blob, blob, blob_sz );
+    memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
+  }
+  memcpy( tail, txn, txn_sz );
+  /* the slot layout, read from the caller's bytes: a blob that was just
+     staged is in the cache from the copy, one read in place from the pass
+     fd_txn_try_submit made before it took the lock.  Should the bytes
+     change between this and the DMA, the front kernel refuses whatever
+     parses to another count than it claims here */
+  unsigned long n_sig = fd_ed25519_gpu_txn_claims( blob, blob_sz, txn, n_txn, (uint32_t *)( tail + txn_sz ) );
+  if( n_sig > g->max_sigs ) return FD_ED25519_ERR_ARG;   /* nothing queued */
+  hipError_t e;
+  int busy = fd_ring_busy( g, sl );
+  int others = sl->mstream && n_sig <= g->mask_max && (g->group_always || busy);
+  hipStream_t st = others ? sl->mstream : sl->stream;
+  *used = st;
+  if( direct ) {
+    if( (e = hipMemcpyAsync( sl->d_blob, blob, blob_sz, hipMemcpyHostToDevice, st )) != hipSuccess )
+      return fd_gpu_fail( "H2D blob (registered)", e );
+    if( !zc && (e = hipMemcpyAsync( sl->d_blob + doff, sl->h_desc, tail_sz, hipMemcpyHostToDevice, st )) != hipSuccess )
+      return fd_gpu_fail( "H2D transactions", e );
+  } else if( (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, doff + tail_sz, hipMemcpyHostToDevice, st )) != hipSuccess )
+    return fd_gpu_fail( "H2D blob+transactions", e );
+  uint8_t const * dt = zc ? (uint8_t const *)sl->h_desc_dev : sl->d_blob + doff;
+  /* nothing to verify: the front kernel's results are final, straight to
+     the pinned results */
+  if( ev && (e = hipEventRecord( ev[0], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+  if( (e = fd_ed25519_gpu_launch_txn_ring_front( n_txn, n_sig, sl->d_blob, blob_sz, (fd_ed25519_gpu_txn_t const *)dt,
+                                                 (uint32_t const *)( dt + txn_sz ), n_sig ? sl->t_res : sl->h_res_dev, sl->t_desc,
+                                                 st )) != hipSuccess )
+    return fd_gpu_fail( "fd_ed25519_gpu_launch_txn_ring_front", e );
+  if( ev && (e = hipEventRecord( ev[1], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+  sl->early = 0;   /* the results are final only after the reduce */
+  if( n_sig ) {
+    int odirect = sl->h_out_dev && n_sig <= g->out_direct_max;
+    int32_t * codes = odirect ? sl->h_out_dev : sl->d_out;
+    if( (e = fd_ed25519_gpu_launch( n_sig, sl->d_blob, blob_sz, sl->t_desc, &sl->work, codes, st,
+                                    g->mode, g->pool_min, g->quad_max, g->oct_max )) != hipSuccess )
+      return fd_gpu_fail( "launch", e );
+    if( ev && (e = hipEventRecord( ev[2], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+    if( (e = fd_ed25519_gpu_launch_txn_ring_reduce( n_txn, n_sig, sl->t_res, codes, sl->h_res_dev, st )) != hipSuccess )
+      return fd_gpu_fail( "fd_ed25519_gpu_launch_txn_ring_reduce", e );
+    if( ev && (e = hipEventRecord( ev[3], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+    if( !odirect && (e = hipMemcpyAsync( sl->h_out, sl->d_out, n_sig * sizeof(int32_t), hipMemcpyDeviceToHost, st )) != hipSuccess )
+      return fd_gpu_fail( "D2H out", e );
+  } else if( ev ) {
+    if( (e = hipEventRecord( ev[2], st )) != hipSuccess || (e = hipEventRecord( ev[3], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+  }
+  if( (e = hipEventRecord( sl->done, st )) != hipSuccess ) return fd_gpu_fail( "event", e );
+  sl->n = n_sig; sl->n_txn = n_txn;
+  return 0;
+}
+
+/* the bounded drain and orphan path of fd_slot_enqueue */
+static int fd_txn_slot_enqueue( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n_txn, void const * blob,
+                                unsigned long blob_sz, fd_ed25519_gpu_txn_t const * txn, hipEvent_t const * ev ) {
+  hipStream_t st = NULL;
+  int err = fd_txn_slot_enqueue_( g, sl, n_txn, blob, blob_sz, txn, &st, ev );
+  if( err && st && fd_wait_query( fd_stream_query, (void *)st, FD_POLL_SPIN_NS, fd_timeout( g ) ) != 1 ) {
+    if( hipEventRecord( sl->done, st ) == hipSuccess ) { sl->ticket = g->next_ticket++; sl->orphan = 1; sl->n_txn = 0UL; }
+    else sl->ticket = ~0UL;
+  }
+  return err;
+}
+
+static int fd_txn_try_submit( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
+                              fd_ed25519_gpu_txn_t const * txn, unsigned long * ticket, int timed ) {
+  if( !g || !ticket || !txn || !n_txn || n_txn > g->max_sigs || n_txn > FD_TXN_MAX || blob_sz > g->max_blob || (blob_sz && !blob) )
+    return FD_ED25519_ERR_ARG;
+  /* A blob that will be read where it lies (a registered region, a slot's
+     staged buffer) is walked once before the ring lock is taken for good:
+     this pass takes the cache misses of a cold blob (one line per
+     transaction, ~17 ns each) and refuses a batch that claims too much
+     before any slot is looked at; the pass that writes the prefix, under
+     the lock, then finds those lines warm (~2 ns each).  A blob that will
+     be copied into a slot is walked after the copy, which warms it. */
+  int in_place = 0;
+  if( blob_sz ) {
+    std::lock_guard<fd_ring_lock> guard( g->lock );
+    in_place = fd_registered( g, blob, blob_sz );
+    for( int s=0; s<g->depth && !in_place; s++ ) in_place = g->slot[s].h_blob == blob;
+  }
+  if( in_place ) {
+    unsigned long n_sig = 0UL;
+    for( unsigned long t=0UL; t<n_txn; t++ ) {
+      n_sig += fd_txn_claim( (uint8_t const *)blob, blob_sz, txn + t );
+      if( n_sig > g->max_sigs ) return FD_ED25519_ERR_ARG;
+    }
+  }
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  int err = fd_txn_ring_ensure( g );   /* allocates only if fd_ed25519_gpu_txns_reserve has not */
+  if( err ) return err;
+  if( timed )
+    for( int k=0; k<4; k++ )
+      if( !g->txn_ring_ev[k] && (e = hipEventCreate( &g->txn_ring_ev[k] )) != hipSuccess ) { g->txn_ring_ev[k] = NULL; return fd_gpu_fail( "txn event", e ); }
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
+  if( !sl ) return 0;                    /* ring full: poll first */
+  err = fd_txn_slot_enqueue( g, sl, n_txn, blob, blob_sz, txn, timed ? g->txn_ring_ev : NULL );
+  sl->staged = 0;                        /* released, submitted or not, as fd_ed25519_gpu_try_submit2 */
+  if( err ) return err;
+  sl->ticket = g->next_ticket++;
+  *ticket = sl->ticket;
+  return 1;
+}
+
+extern "C" int fd_ed25519_gpu_try_submit_txns( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
+                                               fd_ed25519_gpu_txn_t const * txn, unsigned long * ticket ) {
+  return fd_txn_try_submit( g, n_txn, blob, blob_sz, txn, ticket, 0 );
+}
+
+extern "C" int fd_ed25519_gpu_submit_txns( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
+                                           fd_ed25519_gpu_txn_t const * txn, unsigned long * ticket ) {
+  int r = fd_txn_try_submit( g, n_txn, blob, blob_sz, txn, ticket, 0 );
+  return r == 1 ? 0 : r == 0 ? FD_ED25519_ERR_ARG : r;
+}
+
+extern "C" int fd_ed25519_gpu_poll_txns( fd_ed25519_gpu_t * g, unsigned long ticket, fd_ed25519_gpu_txn_result_t * res, int * codes_opt,
+                                         int block ) {
+  if( !g || !ticket || !res ) return FD_ED25519_ERR_ARG;
+  fd_ed25519_gpu_slot * sl = NULL;
+  {
+    std::lock_guard<fd_ring_lock> guard( g->lock );
+    for( int s=0; s<g->depth && !sl; s++ ) if( g->slot[s].ticket == ticket ) sl = &g->slot[s];
+    if( sl && !sl->n_txn ) return FD_ED25519_ERR_ARG;   /* a descriptor ticket: fd_ed25519_gpu_poll's; it stays valid */
+  }
+  if( !sl ) return FD_ED25519_ERR_ARG;
+  if( block & 1 ) {
+    int err = fd_event_wait( sl->done, fd_timeout( g ) );
+    if( err ) return err;               /* timed out or failed; the ticket stays valid */
+  } else {
+    hipError_t e = hipEventQuery( sl->done );
+    if( e == hipErrorNotReady ) return 0;
+    if( e != hipSuccess ) return fd_gpu_fail( "poll", e );
+  }
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  memcpy( res, sl->h_res, sl->n_txn * sizeof(fd_ed25519_gpu_txn_result_t) );
+  if( codes_opt && sl->n ) memcpy( codes_opt, sl->h_out, sl->n * sizeof(int) );
+  sl->ticket = 0; sl->early = 0; sl->n_txn = 0UL;
+  if( block & FD_ED25519_GPU_POLL_KEEP ) sl->staged = 1;   /* lent back to the caller (unstage to free) */
+  return 1;
+}
+
+extern "C" unsigned long fd_ed25519_gpu_txn_ring_allocs( fd_ed25519_gpu_t * g ) {
+  if( !g ) return 0UL;
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  return g->txn_ring_allocs;
+}
+
+extern "C" int fd_ed25519_gpu_txn_ring_timed( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
+                                              fd_ed25519_gpu_txn_t const * txn, fd_ed25519_gpu_txn_result_t * res, float * kernel_ms ) {
+  if( !kernel_ms || !res ) return FD_ED25519_ERR_ARG;
+  unsigned long ticket = 0UL;
+  int r = fd_txn_try_submit( g, n_txn, blob, blob_sz, txn, &ticket, 1 );
+  if( r != 1 ) return r == 0 ? FD_ED25519_ERR_ARG : r;
+  if( (r = fd_ed25519_gpu_poll_txns( g, ticket, res, NULL, 1 )) != 1 ) {
+    if( r < 0 ) fd_abandon_ticket( g, ticket );
+    return r < 0 ? r : FD_ED25519_ERR_GPU;
+  }
+  /* the events are the engine's: two timed calls at once would share them
+     (a diagnostic, as fd_ed25519_gpu_verify_txns_dev_timed) */
+  hipError_t e;
+  if( (e = hipEventElapsedTime( &kernel_ms[0], g->txn_ring_ev[0], g->txn_ring_ev[1] )) != hipSuccess
+   || (e = hipEventElapsedTime( &kernel_ms[1], g->txn_ring_ev[2], g->txn_ring_ev[3] )) != hipSuccess ) return fd_gpu_fail( "elapsed", e );
   return 0;
 }

@@ -6,7 +6,11 @@
    All four kernels are bandwidth- and latency-light next to the verify
    pipeline they feed: the parser reads a few cache lines of each payload
    (the counts, one byte per instruction account), the others 8-24 bytes
-   per transaction and 16 per signature. */
+   per transaction and 16 per signature.
+
+   fd_k_txn_ring_front and fd_k_txn_ring_reduce are the ring's pair
+   (fd_ed25519_gpu_submit_txns): one launch in front of the verify pipeline
+   and one behind it, on a slot layout the host computed. */
 
 #include "fd_ed25519_gpu_txn_private.h"
 #include "fd_txn_core.h"
@@ -141,6 +145,133 @@ fd_k_txn_reduce( uint64_t n_txn, fd_ed25519_gpu_txn_result_t * __restrict__ res,
     int32_t v = c[ k ];
     if( v ) { res[ t ].status = v; return; }
   }
+}
+
+/* The ring's front end (fd_ed25519_gpu_submit_txns): parse and expand in
+   one launch, for batches whose slot layout the host computed
+   (fd_ed25519_gpu_txn_claims): bases[t] is transaction t's first slot,
+   bases[t+1] - bases[t] the slots it claims (its first payload byte),
+   bases[n_txn] = n_sig.  No workgroup reads anything another one writes.
+
+   Lane i of block b parses transaction 256 b + i, writes its result with
+   sig_base = bases[t], and leaves in LDS what its slots need.  After the
+   barrier the block's lanes walk the block's slots [bases[256 b],
+   bases[min(256 (b+1), n_txn)]), one lane per slot, 256 a round: the owner
+   is the last transaction of the block whose base is <= the slot (a
+   binary search over the bases in LDS), so a wave stores 64 consecutive
+   descriptors as one 1 KiB run whatever the counts are.  A transaction
+   that claims slots but does not parse (or, if the bytes changed under the
+   host, parses to another count than it claimed: FD_ED25519_ERR_ARG) gets
+   the fill descriptor in each.  Slots are clamped to [0, n_sig), so bases
+   that are not what the host routine writes cannot send a store outside
+   desc[0, n_sig). */
+#define FD_TXN_RING_PARSED 0x80000000U
+__global__ void __launch_bounds__( FD_TXN_WG )
+fd_k_txn_ring_front( uint32_t n_txn, uint32_t n_sig, uint8_t const * __restrict__ blob, uint64_t blob_sz,
+                     fd_ed25519_gpu_txn_t const * __restrict__ txn, uint32_t const * __restrict__ bases,
+                     fd_ed25519_gpu_txn_result_t * __restrict__ res, uint4 * __restrict__ desc ) {
+  __shared__ uint32_t s_base[ FD_TXN_WG + 1 ];
+  __shared__ uint32_t s_off [ FD_TXN_WG ];
+  __shared__ uint32_t s_sz  [ FD_TXN_WG ];
+  __shared__ uint32_t s_acct[ FD_TXN_WG ];   /* acct_addr_off | FD_TXN_RING_PARSED, or 0: fill */
+  uint32_t t0 = blockIdx.x * (uint32_t)FD_TXN_WG;
+  uint32_t nb = n_txn - t0 < (uint32_t)FD_TXN_WG ? n_txn - t0 : (uint32_t)FD_TXN_WG;   /* the grid covers n_txn: t0 < n_txn */
+  uint32_t i  = threadIdx.x;
+  if( i < nb ) {
+    uint32_t t = t0 + i;
+    fd_ed25519_gpu_txn_t e = txn[ t ];
+    uint32_t base = bases[ t ], claim = bases[ t + 1U ] - base;
+    fd_txn_core_sum_t sum;
+    int32_t status;
+    if( (uint64_t)e.off + (uint64_t)e.sz > blob_sz ) {
+      sum.tag = 0; sum.footprint = 0; sum.reject_line = 0; sum.acct_addr_off = 0; sum.sig_cnt = 0; sum.version = FD_TXN_VLEGACY;
+      status = FD_ED25519_ERR_ARG;
+    } else {
+      unsigned long fp = fd_txn_core_parse( blob + e.off, (unsigned long)e.sz, (void *)0, 0UL, &sum );
+      status = fp ? FD_ED25519_SUCCESS : FD_ED25519_ERR_TXN;
+      if( fp && (uint32_t)sum.sig_cnt != claim ) {   /* not the bytes the host laid the slots out from */
+        sum.tag = 0; sum.footprint = 0; sum.reject_line = 0; sum.acct_addr_off = 0; sum.sig_cnt = 0; sum.version = FD_TXN_VLEGACY;
+        status = FD_ED25519_ERR_ARG;
+      }
+    }
+    uint32_t fp16 = sum.footprint > 0xffffU ? 0xffffU : sum.footprint;
+    uint64_t * r = (uint64_t *)( res + t );
+    r[0] = (uint64_t)(uint32_t)status | ((uint64_t)base << 32);
+    r[1] = sum.tag;
+    r[2] = (uint64_t)fp16 | ((uint64_t)sum.reject_line << 16) | ((uint64_t)sum.sig_cnt << 32) | ((uint64_t)sum.version << 40);
+    s_base[ i ] = base;
+    s_off [ i ] = e.off;
+    s_sz  [ i ] = e.sz;
+    s_acct[ i ] = status == FD_ED25519_SUCCESS ? ( (uint32_t)sum.acct_addr_off | FD_TXN_RING_PARSED ) : 0U;
+    if( i == nb - 1U ) s_base[ nb ] = base + claim;
+  }
+  __syncthreads();
+  uint32_t lo = s_base[ 0 ], hi = s_base[ nb ];
+  if( hi > n_sig ) hi = n_sig;
+  for( uint32_t s=lo+i; s<hi; s+=(uint32_t)FD_TXN_WG ) {
+    /* the last j in [0, nb) with s_base[j] <= s (s_base[0] = lo <= s) */
+    uint32_t a = 0U, b = nb;
+    while( b - a > 1U ) {
+      uint32_t m = ( a + b ) >> 1;
+      if( s_base[ m ] <= s ) a = m; else b = m;
+    }
+    uint32_t k = s - s_base[ a ], cnt = s_base[ a + 1U ] - s_base[ a ], acct = s_acct[ a ];
+    uint4 d = FD_TXN_DESC_FILL;
+    if( ( acct & FD_TXN_RING_PARSED ) && k < cnt ) {
+      uint32_t off = s_off[ a ], msg = 1U + 64U * cnt;
+      d = make_uint4( off + 1U + 64U * k, off + ( acct & 0xffffU ) + 32U * k, off + msg, s_sz[ a ] - msg );
+    }
+    desc[ s ] = d;
+  }
+}
+
+/* fd_k_txn_reduce for the ring: the final result of every transaction goes
+   to `out` (the slot's mapped pinned results), so the host reads them with
+   no copy behind the kernel.  `codes` may be the slot's pinned h_out: the
+   codes are fetched eight at a time, so a transaction of up to eight
+   signatures costs one round trip over the link, not one per signature. */
+__global__ void __launch_bounds__( 256 )
+fd_k_txn_ring_reduce( uint32_t n_txn, uint32_t n_sig, fd_ed25519_gpu_txn_result_t const * __restrict__ res,
+                      int32_t const * __restrict__ codes, fd_ed25519_gpu_txn_result_t * __restrict__ out ) {
+  uint32_t t = blockIdx.x * 256U + threadIdx.x;
+  if( t >= n_txn ) return;
+  uint64_t const * r = (uint64_t const *)( res + t );
+  uint64_t r0 = r[0], r1 = r[1], r2 = r[2];
+  uint32_t cnt = (uint32_t)( r2 >> 32 ) & 0xffU, base = (uint32_t)( r0 >> 32 );
+  int32_t status = (int32_t)(uint32_t)r0;
+  if( cnt && status == FD_ED25519_SUCCESS && base <= n_sig && cnt <= n_sig - base ) {
+    int32_t const * c = codes + base;
+    for( uint32_t k0=0U; k0<cnt && !status; k0+=8U ) {
+      int32_t v[8];
+#pragma unroll
+      for( uint32_t j=0U; j<8U; j++ ) v[j] = k0 + j < cnt ? c[ k0 + j ] : 0;
+#pragma unroll
+      for( uint32_t j=0U; j<8U; j++ ) if( !status && v[j] ) status = v[j];
+    }
+  }
+  uint64_t * o = (uint64_t *)( out + t );
+  o[0] = ( r0 & 0xffffffff00000000UL ) | (uint64_t)(uint32_t)status;
+  o[1] = r1;
+  o[2] = r2;
+}
+
+extern "C" hipError_t
+fd_ed25519_gpu_launch_txn_ring_front( uint64_t n_txn, uint64_t n_sig, uint8_t const * blob, uint64_t blob_sz,
+                                      fd_ed25519_gpu_txn_t const * txn, uint32_t const * bases, fd_ed25519_gpu_txn_result_t * res,
+                                      fd_ed25519_gpu_desc_t * desc, hipStream_t stream ) {
+  if( !n_txn || n_txn > FD_TXN_MAX || n_sig > 0xffffffffUL ) return hipErrorInvalidValue;
+  hipLaunchKernelGGL( fd_k_txn_ring_front, dim3((unsigned)((n_txn + FD_TXN_WG - 1UL) / FD_TXN_WG)), dim3((unsigned)FD_TXN_WG), 0, stream,
+                      (uint32_t)n_txn, (uint32_t)n_sig, blob, blob_sz, txn, bases, res, (uint4 *)desc );
+  return hipGetLastError();
+}
+
+extern "C" hipError_t
+fd_ed25519_gpu_launch_txn_ring_reduce( uint64_t n_txn, uint64_t n_sig, fd_ed25519_gpu_txn_result_t const * res, int32_t const * codes,
+                                       fd_ed25519_gpu_txn_result_t * out, hipStream_t stream ) {
+  if( !n_txn || n_txn > FD_TXN_MAX || n_sig > 0xffffffffUL ) return hipErrorInvalidValue;
+  hipLaunchKernelGGL( fd_k_txn_ring_reduce, dim3((unsigned)((n_txn + 255UL) / 256UL)), dim3(256), 0, stream,
+                      (uint32_t)n_txn, (uint32_t)n_sig, res, codes, out );
+  return hipGetLastError();
 }
 
 extern "C" hipError_t

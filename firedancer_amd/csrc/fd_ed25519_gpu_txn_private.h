@@ -34,6 +34,17 @@ hipError_t fd_ed25519_gpu_launch_txn_front( uint64_t n_txn, uint8_t const * blob
 /* fd_k_txn_reduce: status of every transaction that got slots */
 hipError_t fd_ed25519_gpu_launch_txn_reduce( uint64_t n_txn, fd_ed25519_gpu_txn_result_t * res, int32_t const * codes,
                                              hipStream_t stream );
+/* fd_k_txn_ring_front: the ring's one-launch front end.  bases[0..n_txn]
+   is what fd_ed25519_gpu_txn_claims writes (n_sig = bases[n_txn]); res
+   receives every field, status final for whatever did not parse; desc
+   slots [0, n_sig). */
+hipError_t fd_ed25519_gpu_launch_txn_ring_front( uint64_t n_txn, uint64_t n_sig, uint8_t const * blob, uint64_t blob_sz,
+                                                 fd_ed25519_gpu_txn_t const * txn, uint32_t const * bases,
+                                                 fd_ed25519_gpu_txn_result_t * res, fd_ed25519_gpu_desc_t * desc, hipStream_t stream );
+/* fd_k_txn_ring_reduce: res folded with codes[0, n_sig) into out (mapped
+   pinned memory, or anything else the device writes) */
+hipError_t fd_ed25519_gpu_launch_txn_ring_reduce( uint64_t n_txn, uint64_t n_sig, fd_ed25519_gpu_txn_result_t const * res,
+                                                  int32_t const * codes, fd_ed25519_gpu_txn_result_t * out, hipStream_t stream );
 #ifdef __cplusplus
 }
 #endif

@@ -79,7 +79,10 @@ typedef struct {                                                /* 24 bytes */
    max_txn transactions: two sets (successive calls alternate) of
    per-signature descriptors and codes (max_sigs each), per-transaction
    counts and the scan's partial sums, and the packed call's device-side
-   entries and results.  A tile calls it before sandboxing; without it the
+   entries and results; and, for every ring slot, the scratch of the ring's
+   transaction batches (fd_ed25519_gpu_submit_txns below: max_sigs
+   descriptors and results in HBM and max_sigs pinned results, whatever
+   max_txn is).  A tile calls it before sandboxing; without it the
    first call (and every call with more transactions than any before)
    allocates.  fd_ed25519_gpu_delete frees the scratch.  Returns 0,
    FD_ED25519_ERR_ARG or FD_ED25519_ERR_GPU. */
@@ -185,6 +188,117 @@ fd_ed25519_gpu_verify_txns_dev_timed( fd_ed25519_gpu_t *            gpu,
                                       unsigned long                 txn_out_stride,
                                       void *                        stream,
                                       float *                       kernel_ms );
+
+/* Transactions through the pinned ring: the asynchronous form, on the same
+   slots, tickets, staging, registered-region DMA and CU groups as
+   fd_ed25519_gpu_submit / _try_submit / _poll (fd_ed25519_gpu.h).  Only
+   the ring lock is taken; several batches are in flight at once, each on
+   its slot's own scratch.
+
+   Claimed slots.  A ring batch's slot layout is computed by the host, from
+   the one byte a payload that parses cannot contradict, its first
+   (fd_txn_parse takes signature_cnt from it and rejects anything outside
+   [1, 127]):
+
+     claim(t) = blob[ txn[t].off ]  if the entry lies inside blob[0, blob_sz),
+                                    has sz >= 1 and that byte is in [1, 127],
+              = 0                   otherwise;
+     base(t)  = the sum of claim(u) over u < t;   n_sig = the sum over all t.
+
+   Transaction t owns slots [base(t), base(t) + claim(t)) and the verify
+   pipeline runs on exactly n_sig slots: no scan on the device, no tail.  A
+   transaction that parses has sig_cnt == claim(t).  One that claims slots
+   but does not parse keeps them: they hold the fill descriptor (sig_off =
+   pub_off = 0xffffffff; their codes are FD_ED25519_ERR_ARG), its status is
+   FD_ED25519_ERR_TXN with the parser's reject_line, and sig_cnt, tag and
+   footprint are 0 as everywhere else.
+
+   This is the one difference from fd_ed25519_gpu_verify_txns_dev and
+   _packed: on the ring, sig_base is base(t) as defined here, so an
+   unparsed transaction with a nonzero claim does take slots, and the
+   per-signature codes are indexed by the claim prefix, not by the prefix
+   of the parsed counts.  Every other field is the same. */
+
+/* bases[0..n_txn] <- the exclusive prefix of the claims, bases[n_txn] =
+   n_sig; returns n_sig (as an unsigned long: the prefix itself is 32 bits,
+   enough for the 2^24 transactions of 127 signatures a launch is bounded
+   by).  bases may be NULL: the total only.  Pure host code, no engine, no
+   device: a tile closes a batch with it when the total would pass the
+   engine's max_sigs. */
+unsigned long
+fd_ed25519_gpu_txn_claims( void const *                 blob,
+                           unsigned long                blob_sz,
+                           fd_ed25519_gpu_txn_t const * txn,
+                           unsigned long                n_txn,
+                           uint32_t *                   bases );
+
+/* Submit one batch: 1 submitted (*ticket set), 0 the ring is full (poll
+   first), < 0 an error.  FD_ED25519_ERR_ARG, with nothing queued and every
+   slot as it was: n_txn == 0 or > max_sigs, n_sig (the claimed total) >
+   max_sigs, blob_sz > max_blob, a NULL ticket, txn or (blob_sz != 0) blob.
+   A batch in which nothing claims a slot is valid: the parser runs alone.
+
+   blob is used as fd_ed25519_gpu_try_submit uses it: read in place by DMA
+   if it lies in a region given to fd_ed25519_gpu_register, taken as it
+   lies if it is a slot's staged buffer (fd_ed25519_gpu_stage; the stage is
+   released on every return that reached a slot, as fd_ed25519_gpu_
+   try_submit2 releases it), copied into a slot's pinned buffer otherwise;
+   txn is copied during the call.  The engine's mode and schedule knobs
+   apply as to any ring batch, and the CU-group rule with n = n_sig.
+   Without fd_ed25519_gpu_txns_reserve the first submit allocates the
+   slots' scratch. */
+int
+fd_ed25519_gpu_try_submit_txns( fd_ed25519_gpu_t *           gpu,
+                                unsigned long                n_txn,
+                                void const *                 blob,
+                                unsigned long                blob_sz,
+                                fd_ed25519_gpu_txn_t const * txn,
+                                unsigned long *              ticket );
+
+/* The same; 0, or FD_ED25519_ERR_ARG when the ring is full, as
+   fd_ed25519_gpu_submit. */
+int
+fd_ed25519_gpu_submit_txns( fd_ed25519_gpu_t *           gpu,
+                            unsigned long                n_txn,
+                            void const *                 blob,
+                            unsigned long                blob_sz,
+                            fd_ed25519_gpu_txn_t const * txn,
+                            unsigned long *              ticket );
+
+/* Collect a transaction ticket: res takes the batch's n_txn results,
+   codes_opt (NULL, or n_sig ints) the per-signature codes by claimed slot.
+   block as fd_ed25519_gpu_poll's: bit 0 waits (bounded by the engine's
+   timeout), FD_ED25519_GPU_POLL_KEEP leaves the slot's pinned buffers
+   staged to the caller.  Returns 1 collected, 0 not ready, < 0 an error
+   (the ticket stays valid).  Tickets come from the engine's one counter:
+   this call on a descriptor ticket, and fd_ed25519_gpu_poll with out !=
+   NULL on a transaction ticket, return FD_ED25519_ERR_ARG and leave the
+   ticket as it was; fd_ed25519_gpu_poll( gpu, ticket, NULL, block ) drains
+   either kind. */
+int
+fd_ed25519_gpu_poll_txns( fd_ed25519_gpu_t *            gpu,
+                          unsigned long                 ticket,
+                          fd_ed25519_gpu_txn_result_t * res,
+                          int *                         codes_opt,
+                          int                           block );
+
+/* Diagnostics: the number of ring slots whose transaction scratch has been
+   allocated so far (0, then the ring's depth after fd_ed25519_gpu_
+   txns_reserve or the first submit; it never moves afterwards). */
+unsigned long
+fd_ed25519_gpu_txn_ring_allocs( fd_ed25519_gpu_t * gpu );
+
+/* Diagnostics (tools/txn_bench.py --ring): one batch submitted and polled,
+   with HIP events around fd_k_txn_ring_front and fd_k_txn_ring_reduce;
+   their durations (ms) go to kernel_ms[2].  One caller at a time. */
+int
+fd_ed25519_gpu_txn_ring_timed( fd_ed25519_gpu_t *            gpu,
+                               unsigned long                 n_txn,
+                               void const *                  blob,
+                               unsigned long                 blob_sz,
+                               fd_ed25519_gpu_txn_t const *  txn,
+                               fd_ed25519_gpu_txn_result_t * res,
+                               float *                       kernel_ms );
 
 #ifdef __cplusplus
 }
