@@ -44,6 +44,10 @@ TXN_RESULT_DTYPE = np.dtype([("status", "<i4"), ("sig_base", "<u4"), ("tag", "<u
 _lib = None
 
 
+class Stages:
+    """what Engine.debug_stages read back from one launch"""
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -179,6 +183,8 @@ def lib() -> ctypes.CDLL:
         L.fd_ed25519_gpu_debug_k.restype = ip
         L.fd_ed25519_gpu_debug_verify_dig.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp, vp]
         L.fd_ed25519_gpu_debug_verify_dig.restype = ip
+        L.fd_ed25519_gpu_debug_stages.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.fd_ed25519_gpu_debug_stages.restype = ip
         L.fd_ed25519_gpu_debug_fe.argtypes = [vp, ip, ul, vp, vp, vp]
         L.fd_ed25519_gpu_debug_fe.restype = ip
         L.fd_ed25519_gpu_sha512_packed.argtypes = [vp, ul, vp, ul, vp, vp, ip]
@@ -474,6 +480,45 @@ class Engine:
         if err:
             raise EngineError(f"debug_verify_dig: {strerror(err)}: {last_error()}")
         return codes, k, st
+
+    def debug_stages(self, blob: np.ndarray, desc: np.ndarray, dig=None) -> "Stages":
+        """Diagnostics (fd_ed25519_gpu_debug_stages): one verify launch on the schedule
+        the engine's mode and knobs give a batch of n, with the stages it leaves in the
+        HBM working set read back.  dig None: the product's front end (real SHA-512);
+        dig [n,64] uint8: the chosen-digest front end of debug_verify_dig.  Returns a
+        Stages: codes[n], status[n] (prep's), pstat[2n], pts[2n,40] (A rows, then R
+        rows), op_start[n], ops[n,512], tab[n,8,4,12] or None, fin[n,40] or None (pooled
+        schedule only), schedule ("uniform", "pooled", "quad", "oct") and ops_sigmajor
+        (the layout the device used; ops is delivered signature-major either way)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        desc = np.ascontiguousarray(desc, dtype=DESC_DTYPE)
+        n = len(desc)
+        if dig is not None:
+            dig = np.ascontiguousarray(dig, dtype=np.uint8)
+            if dig.size != 64 * n:
+                raise EngineError(f"debug_stages: dig holds {dig.size} bytes, not 64 per signature ({64 * n})")
+        s = Stages()
+        s.codes = np.zeros(n, np.int32)
+        s.status = np.zeros(n, np.int32)
+        s.pstat = np.zeros(2 * n, np.int32)
+        s.pts = np.zeros((2 * n, 40), np.int32)
+        s.op_start = np.zeros(n, np.int32)
+        s.ops = np.zeros((n, 512), np.uint8)
+        s.tab = np.zeros((n, 8, 4, 12), np.int32)
+        s.fin = np.zeros((n, 40), np.int32)
+        info = np.zeros(4, np.int32)
+        err = lib().fd_ed25519_gpu_debug_stages(self._h, n, _p(blob), blob.nbytes, _p(desc), _p(dig) if dig is not None and n else None,
+                                                _p(s.codes), _p(s.status), _p(s.pstat), _p(s.pts), _p(s.op_start), _p(s.ops),
+                                                _p(s.tab), _p(s.fin), _p(info))
+        if err:
+            raise EngineError(f"debug_stages: {strerror(err)}: {last_error()}")
+        s.schedule = ("uniform", "pooled", "quad", "oct")[int(info[0])]
+        s.ops_sigmajor = bool(info[1])
+        if not info[2]:
+            s.tab = None
+        if not info[3]:
+            s.fin = None
+        return s
 
     def debug_fe(self, op: int, f: np.ndarray, g: np.ndarray) -> np.ndarray:
         """Diagnostics: the device field products (fd_k_debug_fe op 0-6, op 7 the oct DSM's half product) of

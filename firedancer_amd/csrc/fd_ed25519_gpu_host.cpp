@@ -1308,6 +1308,127 @@ done:
   return err;
 }
 
+/* Diagnostics: one verify launch with the stages it leaves in the working
+   set (dev_work[0]) read back -- prep's status, the point statuses and
+   decompressed points, the op streams, the Ai tables and the pooled DSM's
+   final p1p1 rows -- each in one layout whatever the schedule's own (see
+   fd_ed25519_gpu_diag.h).  dig NULL: the product's front
+   (fd_ed25519_gpu_launch_front, real SHA-512); else
+   fd_ed25519_gpu_launch_front_dig as fd_ed25519_gpu_debug_verify_dig.
+   Host code only: the kernels run as in any other launch. */
+extern "C" int fd_ed25519_gpu_debug_stages( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
+                                            fd_ed25519_gpu_desc_t const * desc, uint8_t const * dig,
+                                            int * codes_out, int * status_out, int * pstat_out, int * pts_out,
+                                            int * op_start_out, uint8_t * ops_out, int * tab_out, int * fin_out,
+                                            int * info_out ) {
+  if( !g || n > g->max_sigs || blob_sz > g->max_blob || (n && !desc) || (blob_sz && !blob) ) return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  fd_knobs kn = fd_knobs_get( g );     /* before the locks below: fd_knobs_get takes g->lock itself */
+  /* the schedule, by fd_ed25519_gpu_launch_front's and _back's predicates */
+  int const portable = (kn.mode & 0xff) == FD_ED25519_GPU_MODE_PORTABLE;
+  int const pooled   = n >= kn.pool_min;
+  int const oct      = !pooled && !portable && n <= kn.oct_max;
+  int const quad     = !pooled && !portable && n <= kn.quad_max;
+  int const sched    = pooled ? FD_ED25519_GPU_SCHED_POOLED : oct ? FD_ED25519_GPU_SCHED_OCT
+                     : quad ? FD_ED25519_GPU_SCHED_QUAD : FD_ED25519_GPU_SCHED_UNIFORM;
+  int const sigmajor = oct || quad;    /* the latency front end's signature-major op rows */
+  int const has_tab  = !sigmajor;      /* fd_k_dsm (AoS per signature) or fd_k_dsm_setup ([entry][n]) */
+  /* both engine locks, dev_lock first (fd_ed25519_gpu_debug_k) */
+  std::lock_guard<std::mutex> dguard( g->dev_lock );
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
+  if( !sl ) return FD_ED25519_ERR_ARG;
+  hipStream_t st = sl->stream;
+  unsigned long doff = fd_desc_off( blob_sz );
+  memcpy( sl->h_blob, blob, blob_sz );
+  memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
+  memcpy( sl->h_blob + doff, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
+  fd_ed25519_gpu_desc_t const * d_desc = (fd_ed25519_gpu_desc_t const *)(sl->d_blob + doff);
+  fd_ed25519_gpu_work_t const * w = &g->dev_work[0];
+  /* device scratch: state words [n][8], codes [n]; the host copy holds the
+     stages behind them, each only if asked for */
+  unsigned long const o_c = 64UL * n, dsz = 68UL * n;
+  unsigned long o = dsz;
+  unsigned long const o_st  = o; o += 4UL * n;
+  unsigned long const o_ps  = o; o += pstat_out    ? 8UL * n : 0UL;
+  unsigned long const o_os  = o; o += op_start_out ? 4UL * n : 0UL;
+  unsigned long const o_pts = o; o += pts_out      ? 320UL * n : 0UL;
+  unsigned long const o_fin = o; o += fin_out && pooled ? 160UL * n : 0UL;
+  unsigned long const o_ops = o; o += ops_out      ? (unsigned long)FD_OPS_MAX * n : 0UL;
+  unsigned long const o_tab = o; o += tab_out && has_tab ? 4UL * (unsigned long)FD_TAB_SIG * n : 0UL;
+  uint8_t * h = (uint8_t *)malloc( o );
+  uint8_t * d = NULL;
+  int err = 0;
+  if( !h ) return FD_ED25519_ERR_GPU;
+  if( (e = hipMalloc( (void **)&d, dsz )) != hipSuccess ) { free( h ); return fd_gpu_fail( "debug_stages alloc", e ); }
+  if( dig ) {
+    uint64_t * hw = (uint64_t *)h;
+    for( unsigned long i=0; i<8UL*n; i++ ) {
+      uint64_t x = 0UL;
+      for( int b=0; b<8; b++ ) x = (x << 8) | (uint64_t)dig[8UL*i + (unsigned long)b];
+      hw[i] = x;
+    }
+  }
+  if( (e = fd_dev_serial_begin( g, st )) != hipSuccess
+   || (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, doff + n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess
+   || (dig && (e = hipMemcpyAsync( d, h, 64UL * n, hipMemcpyHostToDevice, st )) != hipSuccess)
+   || (e = hipMemsetAsync( d + o_c, 0x7f, 4UL * n, st )) != hipSuccess       /* no code: a row the DSM left unwritten shows */
+   || (e = dig ? fd_ed25519_gpu_launch_front_dig( n, sl->d_blob, blob_sz, d_desc, (uint64_t const *)d, w, (uint64_t *)NULL, st,
+                                                  kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )
+               : fd_ed25519_gpu_launch_front( n, sl->d_blob, blob_sz, d_desc, w, st, NULL,
+                                              kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )) != hipSuccess
+   || (e = hipMemcpyAsync( h + o_st, w->status, 4UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess   /* prep's, before the DSM settles it */
+   || (e = fd_ed25519_gpu_launch_back( n, sl->d_blob, d_desc, w, (int32_t *)(d + o_c), st, NULL,
+                                       kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )) != hipSuccess
+   || (e = hipMemcpyAsync( h + o_c, d + o_c, 4UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess
+   || (pstat_out    && (e = hipMemcpyAsync( h + o_ps,  w->pstat,    8UL * n,   hipMemcpyDeviceToHost, st )) != hipSuccess)
+   || (op_start_out && (e = hipMemcpyAsync( h + o_os,  w->op_start, 4UL * n,   hipMemcpyDeviceToHost, st )) != hipSuccess)
+   || (pts_out      && (e = hipMemcpyAsync( h + o_pts, w->pts,      320UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess)
+   || (o_ops != o_fin && (e = hipMemcpyAsync( h + o_fin, w->fin,    160UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess)
+   || (ops_out      && (e = hipMemcpyAsync( h + o_ops, w->ops, (unsigned long)FD_OPS_MAX * n, hipMemcpyDeviceToHost, st )) != hipSuccess)
+   || (o != o_tab   && (e = hipMemcpyAsync( h + o_tab, w->tab, 4UL * (unsigned long)FD_TAB_SIG * n, hipMemcpyDeviceToHost, st )) != hipSuccess)
+   || (e = hipEventRecord( sl->done, st )) != hipSuccess
+   || (e = fd_dev_serial_end( g, st )) != hipSuccess ) { err = fd_gpu_fail( "debug_stages", e ); (void)hipStreamSynchronize( st ); goto done; }
+  if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) {
+    sl->ticket = g->next_ticket++; sl->orphan = 1;
+    free( h );
+    return err;     /* the device buffer may still be in use: leaked */
+  }
+  if( codes_out )    memcpy( codes_out,    h + o_c,  4UL * n );
+  if( status_out )   memcpy( status_out,   h + o_st, 4UL * n );
+  if( pstat_out )    memcpy( pstat_out,    h + o_ps, 8UL * n );
+  if( op_start_out ) memcpy( op_start_out, h + o_os, 4UL * n );
+  if( pts_out ) {      /* device: [40][2n] -> [2n][40] */
+    int32_t const * s = (int32_t const *)(h + o_pts);
+    for( unsigned long j=0; j<2UL*n; j++ )
+      for( unsigned long k=0; k<40UL; k++ ) pts_out[40UL*j + k] = s[k*2UL*n + j];
+  }
+  if( ops_out ) {      /* device: [n][FD_OPS_MAX] (latency front end) or step-major [FD_OPS_MAX][n] */
+    uint8_t const * s = h + o_ops;
+    if( sigmajor ) memcpy( ops_out, s, (unsigned long)FD_OPS_MAX * n );
+    else
+      for( unsigned long i=0; i<n; i++ )
+        for( unsigned long t=0; t<(unsigned long)FD_OPS_MAX; t++ ) ops_out[(unsigned long)FD_OPS_MAX*i + t] = s[t*n + i];
+  }
+  if( tab_out && has_tab ) {   /* device: [n][8][48] (fd_k_dsm) or [8][n][48] (fd_k_dsm_setup) */
+    int32_t const * s = (int32_t const *)(h + o_tab);
+    if( !pooled ) memcpy( tab_out, s, 4UL * (unsigned long)FD_TAB_SIG * n );
+    else
+      for( unsigned long i=0; i<n; i++ )
+        for( unsigned long en=0; en<8UL; en++ )
+          memcpy( tab_out + i*(unsigned long)FD_TAB_SIG + en*(unsigned long)FD_TAB_ENTRY,
+                  s + (en*n + i)*(unsigned long)FD_TAB_ENTRY, 4UL * (unsigned long)FD_TAB_ENTRY );
+  }
+  if( fin_out && pooled ) memcpy( fin_out, h + o_fin, 160UL * n );
+  if( info_out ) { info_out[0] = sched; info_out[1] = sigmajor; info_out[2] = has_tab; info_out[3] = pooled; }
+done:
+  hipFree( d );
+  free( h );
+  return err;
+}
+
 /* SHA-512 / SHA-384 of n messages blob[msg_off..+msg_sz) (sig_off and
    pub_off unused) on the device; hash_out receives n digests of 64 (48)
    bytes back to back.  Synchronous. */

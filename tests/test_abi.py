@@ -5,6 +5,7 @@ import ctypes
 import glob
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -118,3 +119,40 @@ def test_feeder_wait_keeps_arrays_until_final_state():
     with pytest.raises(fa.EngineError):
         f.wait(j2, 0)
     assert ctypes.addressof(j2) not in f._keep
+
+
+STAGES_PROTO = """
+#include "fd_ed25519_gpu_diag.h"
+int (*p_stages)( fd_ed25519_gpu_t *, unsigned long, void const *, unsigned long, fd_ed25519_gpu_desc_t const *,
+                 unsigned char const *, int *, int *, int *, int *, int *, unsigned char *, int *, int *, int * )
+  = fd_ed25519_gpu_debug_stages;
+_Static_assert( FD_ED25519_GPU_SCHED_UNIFORM == 0 && FD_ED25519_GPU_SCHED_POOLED == 1 && FD_ED25519_GPU_SCHED_QUAD == 2
+                && FD_ED25519_GPU_SCHED_OCT == 3, "schedule ids" );
+"""
+
+
+def test_debug_stages_abi(tmp_path):
+    """fd_ed25519_gpu_debug_stages (include/fd_ed25519_gpu_diag.h): the header is C with
+    the documented prototype, the symbol is exported, and a call without an engine is
+    refused before anything is written or a device is touched -- whatever n, also 0.
+    The argument checks that need an engine (n > max_sigs, blob_sz > max_blob, NULL desc
+    with n > 0, n == 0) are in tests/test_gpu_stages.py::test_stages_args."""
+    src = tmp_path / "stages.c"
+    src.write_text(STAGES_PROTO)
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-pedantic", "-I" + os.path.join(ROOT, "include"), "-c", str(src),
+                    "-o", str(tmp_path / "stages.o")], check=True, capture_output=True)
+    L = fa.lib()
+    assert callable(fa.Engine.debug_stages)
+    n = 3
+    blob = np.zeros(96 * n + 64, np.uint8)
+    desc = np.zeros(n, fa.DESC_DTYPE)
+    dig = np.zeros(64 * n, np.uint8)
+    # codes, status, pstat, pts, op_start, ops, tab, fin, info: their sizes in bytes
+    outs = [np.full(k, 0x55, np.uint8) for k in (4 * n, 4 * n, 8 * n, 320 * n, 4 * n, 512 * n, 1536 * n, 160 * n, 16)]
+    for cnt in (n, 0, 1 << 40):
+        for d in (fa._p(dig), None):
+            for ds in (fa._p(desc), None):
+                r = L.fd_ed25519_gpu_debug_stages(None, cnt, fa._p(blob), blob.nbytes, ds, d, *[fa._p(o) for o in outs])
+                assert r == fa.ERR_ARG, (cnt, r)
+                assert L.fd_ed25519_gpu_debug_stages(None, cnt, None, 0, ds, d, *([None] * 9)) == fa.ERR_ARG
+    assert all((o == 0x55).all() for o in outs)
