@@ -2,7 +2,16 @@
 section 8f row 3).  Digests are checked against NIST CAVP vectors and the
 reference's own vectors (tests/golden/sha512_vectors.json) and against
 the reference's fd_sha512 / fd_sha384 compiled in place (oracle/_ref) on
-random messages at every padding boundary."""
+random messages whose lengths sit at and beside every padding boundary.
+
+What this module does not vary is where a message starts: Engine.sha512
+packs every message at a multiple of 8 bytes (zero filled), and so does
+fd_sha512_gpu_batch_add, so fd_k_sha512_batch sees messages at offsets 0 or
+8 mod 16 only, its realignment shift (d & 3) * 8 is always 0, and the bytes
+after a message are zeros.  Every length 0..401 at every offset 0..15 mod
+16 with random neighbours, through fd_ed25519_gpu_sha512_packed with the
+test's own descriptors, is tests/test_gpu_hash_paths.py::
+test_plain_sha512_any_offset."""
 import ctypes
 
 import numpy as np
