@@ -133,11 +133,43 @@ core_txn_sweep_cmp( uint8_t const * payload, unsigned long n, parser_fn other, l
 }
 
 #ifdef TXN_HARNESS_MAIN
-/* argv: fixture files.  The sweep of each through every mode of the core,
-   then a few synthetic shapes (empty, oversized, deep compact-u16s). */
+/* --grid's file: payloads one after another, each behind its length as a
+   little-endian u32 (tests/txn_grid.py write_file); each through every mode
+   of the core.  Returns the number of payloads, -1 after printing why. */
+static long run_grid( char const * path ) {
+  FILE * f = fopen( path, "rb" );
+  if( !f ) { printf( "cannot open %s\n", path ); return -1L; }
+  long n = 0;
+  uint8_t len[4];
+  while( fread( len, 1, 4, f ) == 4 ) {
+    unsigned long sz = (unsigned long)len[0] | ((unsigned long)len[1] << 8) | ((unsigned long)len[2] << 16) | ((unsigned long)len[3] << 24);
+    if( sz > (1UL<<20) ) { printf( "%s: payload %ld claims %lu bytes\n", path, n, sz ); fclose( f ); return -1L; }
+    uint8_t * p = (uint8_t *)malloc( sz ? sz : 1UL );
+    if( !p ) abort();
+    if( fread( p, 1, sz, f ) != sz ) { printf( "%s: payload %ld is cut short\n", path, n ); free( p ); fclose( f ); return -1L; }
+    int bad = core_txn_cmp( p, sz, NULL );
+    free( p );
+    if( bad ) { printf( "%s: payload %ld (%lu bytes) disagrees, check %d\n", path, n, sz, bad ); fclose( f ); return -1L; }
+    n++;
+  }
+  fclose( f );
+  return n;
+}
+
+/* argv: fixture files, and optionally --grid FILE.  The sweep of each
+   fixture through every mode of the core, the grid's payloads, then a few
+   synthetic shapes (empty, oversized, deep compact-u16s). */
 int main( int argc, char ** argv ) {
   unsigned long swept = 0;
+  long in_grid = 0;
   for( int a=1; a<argc; a++ ) {
+    if( !strcmp( argv[a], "--grid" ) ) {
+      if( a + 1 >= argc ) { printf( "--grid needs a file\n" ); return 2; }
+      in_grid = run_grid( argv[++a] );
+      if( in_grid < 0 ) return 1;
+      printf( "%ld grid payloads ok\n", in_grid );
+      continue;
+    }
     FILE * f = fopen( argv[a], "rb" );
     if( !f ) { printf( "cannot open %s\n", argv[a] ); return 2; }
     static uint8_t p[ 1<<16 ];
