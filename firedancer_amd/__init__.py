@@ -243,6 +243,10 @@ def lib() -> ctypes.CDLL:
         L.fd_ed25519_gpu_multi_new_ex.restype = vp
         L.fd_ed25519_gpu_multi_feeder.argtypes = [vp, ip]
         L.fd_ed25519_gpu_multi_feeder.restype = vp
+        L.fd_ed25519_gpu_sha512_ptrs.argtypes = [vp, ul, vp, vp, vp, ip]
+        L.fd_ed25519_gpu_sha512_ptrs.restype = ip
+        L.fd_sha512_gpu_long_geometry.argtypes = [ul, ul, ul, ctypes.POINTER(ctypes.c_ulong), ctypes.POINTER(ctypes.c_ulong)]
+        L.fd_sha512_gpu_long_geometry.restype = ip
         L.fd_sha512_gpu_batch_new.argtypes = [vp, ip]
         L.fd_sha512_gpu_batch_new.restype = vp
         L.fd_sha512_gpu_batch_delete.argtypes = [vp]
@@ -305,6 +309,30 @@ def strerror(err: int) -> str:
 
 def last_error() -> str:
     return (lib().fd_ed25519_gpu_last_error() or b"").decode()
+
+
+def sha512_long_geometry(max_blob: int, max_sigs: int, m: int = 1):
+    """fd_sha512_gpu_long_geometry: (G, C) of the long hash path, or None
+    where m is not in [1, G] (G 0: a blob that cannot hold one block)."""
+    G, C = ctypes.c_ulong(0), ctypes.c_ulong(0)
+    if lib().fd_sha512_gpu_long_geometry(max_blob, max_sigs, m, ctypes.byref(G), ctypes.byref(C)):
+        return None
+    return G.value, C.value
+
+
+def _sha512_ptrs(handle, msgs, is384: bool = False) -> list:
+    """fd_ed25519_gpu_sha512_ptrs on an engine handle (None: the default engine)"""
+    n = len(msgs)
+    keep = [m if isinstance(m, np.ndarray) else np.frombuffer(bytes(m), np.uint8) for m in msgs]
+    MP = ctypes.c_void_p * max(n, 1)
+    mp = MP(*[m.ctypes.data if len(m) else None for m in keep])
+    sz = (ctypes.c_ulong * max(n, 1))(*[len(m) for m in keep])
+    hsz = 48 if is384 else 64
+    out = np.zeros(max(n, 1) * hsz, np.uint8)
+    err = lib().fd_ed25519_gpu_sha512_ptrs(handle, n, mp, sz, _p(out), 1 if is384 else 0)
+    if err:
+        raise EngineError(f"sha512_ptrs: {strerror(err)}: {last_error()}")
+    return [out[i * hsz:(i + 1) * hsz].tobytes() for i in range(n)]
 
 
 class Engine:
@@ -725,6 +753,11 @@ class Engine:
         if err:
             raise EngineError(f"sha512_packed: {strerror(err)}: {last_error()}")
         return [out[i * hsz:(i + 1) * hsz].tobytes() for i in range(n)]
+
+    def sha512_any(self, msgs, is384: bool = False) -> list:
+        """fd_ed25519_gpu_sha512_ptrs: SHA-512 (SHA-384) digests of byte
+        strings of any length (past max_blob: the long path)."""
+        return _sha512_ptrs(self._h, msgs, is384)
 
     @property
     def mode(self) -> int:

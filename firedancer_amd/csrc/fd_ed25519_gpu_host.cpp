@@ -30,6 +30,7 @@
 #include "fd_ed25519_gpu_sign_private.h"
 #include "fd_ed25519_gpu_txn_private.h"
 #include "fd_ed25519_gpu_txn_claim.h"
+#include "fd_sha512_gpu_private.h"
 
 #define FD_GPU_DEPTH_DEFAULT 3
 #define FD_GPU_DEPTH_MAX     8
@@ -170,6 +171,7 @@ struct fd_ed25519_gpu_slot {
   int                     retiring; /* its codes were taken early: reclaimed once its event completes */
   uint8_t *               h_dig;    /* pinned digests (SHA-512 batch), allocated on first use */
   uint8_t *               h_sgn;    /* pinned signing results (100 B per signature), allocated on first use */
+  hipEvent_t              sha_ev[2]; /* long plain hashes: the kernel that read half h of the blob has finished (first use) */
   /* transaction batches on the ring (fd_ed25519_gpu_submit_txns): the
      slot's own scratch, allocated by fd_txn_ring_ensure */
   unsigned long                 n_txn;     /* transactions of the batch in flight; 0: a descriptor batch */
@@ -488,6 +490,7 @@ extern "C" void fd_ed25519_gpu_delete( fd_ed25519_gpu_t * g ) {
     if( sl->d_work_base ) hipFree( sl->d_work_base );
     if( sl->stream ) hipStreamDestroy( sl->stream );
     if( sl->done   ) hipEventDestroy( sl->done );
+    for( int h=0; h<2; h++ ) if( sl->sha_ev[h] ) hipEventDestroy( sl->sha_ev[h] );
   }
   for( int i=0; i<FD_DEV_STATS_MAX; i++ )
     for( int k=0; k<FD_EV_CNT; k++ ) if( g->dev_ev[i][k] ) hipEventDestroy( g->dev_ev[i][k] );
@@ -1658,6 +1661,110 @@ static int fd_run_long( fd_ed25519_gpu_t * g, unsigned long cnt, fd_long_req con
   if( err ) (void)hipStreamSynchronize( sl->stream );      /* a failed enqueue: what was queued drains before the slot is lent again */
   fd_ed25519_gpu_unstage( g, vb );
   return err;
+}
+
+/* ---- Long plain hashes ---------------------------------------------------
+
+   SHA-512 / SHA-384 of messages too large for a staging blob (or a 32-bit
+   descriptor): the reference's batch API has no restriction on sz
+   (src/ballet/sha256/fd_sha256.h:191-192).  As the long verify path above,
+   the padded stream moves through a staged slot's pinned blob in pieces
+   and the chaining states stay in the slot's work.fin rows; unlike it, the
+   last piece of a message leaves its digest, big endian, in its row
+   (fd_k_sha512_pieces), so one D2H copy per group and a memcpy per message
+   deliver the results.  With FD_SHA_LONG_PINGPONG the blob is two halves
+   (fd_sha512_gpu_pack.h) and the host packs one while the device hashes
+   the other; the library ships the single buffer, which measured no slower
+   (fd_sha512_gpu_private.h). */
+
+/* the kernel that read a half has finished, so the half may be repacked;
+   on a timeout the slot is given up as in fd_long_wait, its done event
+   queued behind what is still in flight (if even that fails the slot stays
+   staged: lost to the engine rather than lent out under a running kernel) */
+static int fd_sha_half_wait( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, hipEvent_t ev ) {
+  int err = fd_event_wait( ev, fd_timeout( g ) );
+  if( err && hipEventRecord( sl->done, sl->stream ) == hipSuccess ) {
+    std::lock_guard<fd_ring_lock> guard( g->lock );
+    sl->ticket = g->next_ticket++; sl->orphan = 1; sl->staged = 0;
+  }
+  return err;
+}
+
+extern "C" int fd_sha512_gpu_long( fd_ed25519_gpu_t * g, unsigned long cnt, fd_sha_long_req_t const * rq, int is384 ) {
+  if( !g ) return FD_ED25519_ERR_GPU;
+  if( !cnt ) return 0;
+  fd_sha_long_geom_t geo;
+  (void)fd_sha_long_geom( g->max_blob, g->max_sigs, 1UL, FD_SHA_LONG_PINGPONG, &geo );
+  unsigned long const G = geo.G;
+  if( !G ) {
+    snprintf( fd_gpu_err, sizeof(fd_gpu_err), "long hash: a blob of %lu bytes cannot hold one 128-byte block and its piece entry", g->max_blob );
+    return FD_ED25519_ERR_ARG;
+  }
+  void * vb; fd_ed25519_gpu_desc_t * dd;
+  int err = fd_stage_wait( g, &vb, &dd );
+  if( err ) return err;
+  fd_ed25519_gpu_slot * sl = fd_slot_of( g, vb );
+  if( !sl ) { fd_ed25519_gpu_unstage( g, vb ); return FD_ED25519_ERR_GPU; }
+  hipError_t e = hipSetDevice( g->device );
+  /* the slot's two events and its pinned digests come with its first long hash (as h_dig with the first packed one) */
+  for( int h=0; h<2 && e == hipSuccess; h++ ) if( !sl->sha_ev[h] ) e = hipEventCreateWithFlags( &sl->sha_ev[h], hipEventDisableTiming );
+  if( e == hipSuccess && !sl->h_dig ) e = hipHostMalloc( (void **)&sl->h_dig, g->max_sigs * 64UL, hipHostMallocDefault );
+  if( e != hipSuccess ) { fd_ed25519_gpu_unstage( g, vb ); return fd_gpu_fail( "long hash: setup", e ); }
+  uint64_t * d_st = (uint64_t *)sl->work.fin;              /* 160 B of scratch per signature >= the 64 B row */
+  uint32_t const fl = is384 ? FD_SHA_PIECE_384 : 0U;
+  unsigned long const hsz = is384 ? 48UL : 64UL;
+  std::vector<unsigned long> tot( G ), pos( G );           /* blocks of each stream, and how many are packed */
+  for( unsigned long i0=0; i0<cnt && !err; i0+=G ) {
+    unsigned long m = cnt - i0 < G ? cnt - i0 : G;
+    (void)fd_sha_long_geom( g->max_blob, g->max_sigs, m, FD_SHA_LONG_PINGPONG, &geo );
+    unsigned long C = geo.C, left = m, longest = 0UL;
+    for( unsigned long j=0; j<m; j++ ) {
+      tot[j] = fd_sha_long_blocks( rq[ i0 + j ].sz ); pos[j] = 0UL;
+      if( tot[j] > longest ) longest = tot[j];
+    }
+    if( C > longest ) C = longest;                         /* a group of short streams copies no empty blocks */
+    unsigned long const toff = m * C * 128UL, half_sz = toff + m * sizeof(fd_sha_lpiece_t);
+    for( unsigned long launch=0; left; launch++ ) {
+      unsigned long h = launch % geo.nhalf, off = h * half_sz;
+      if( launch >= geo.nhalf && (err = fd_sha_half_wait( g, sl, sl->sha_ev[h] )) ) return err;
+      fd_sha_lpiece_t * pc = (fd_sha_lpiece_t *)( sl->h_blob + off + toff );
+      for( unsigned long j=0; j<m; j++ ) {
+        fd_sha_long_req_t const & r = rq[ i0 + j ];
+        unsigned long nb = tot[j] - pos[j];
+        if( nb > C ) nb = C;
+        pc[j].off = off + j * C * 128UL; pc[j].nblk = (uint32_t)nb;
+        pc[j].flags = fl | ( pos[j] ? 0U : FD_SHA_PIECE_FIRST ) | ( pos[j] + nb == tot[j] ? FD_SHA_PIECE_LAST : 0U );
+        if( nb ) {
+          fd_sha_long_pack( sl->h_blob + off + j * C * 128UL, (uint8_t const *)r.data, r.sz, pos[j] * 128UL, nb * 128UL );
+          pos[j] += nb;
+          if( pos[j] == tot[j] ) left--;
+        }
+      }
+      if( (e = hipMemcpyAsync( sl->d_blob + off, sl->h_blob + off, half_sz, hipMemcpyHostToDevice, sl->stream )) != hipSuccess
+       || (e = fd_sha512_gpu_launch_pieces( (uint32_t)m, d_st, sl->d_blob, (fd_sha_lpiece_t const *)( sl->d_blob + off + toff ), sl->stream )) != hipSuccess
+       || (e = hipEventRecord( sl->sha_ev[h], sl->stream )) != hipSuccess ) {
+        err = fd_gpu_fail( "long hash: piece", e ); break;
+      }
+    }
+    if( err ) break;
+    if( (e = hipMemcpyAsync( sl->h_dig, d_st, m * 64UL, hipMemcpyDeviceToHost, sl->stream )) != hipSuccess ) {
+      err = fd_gpu_fail( "long hash: D2H digests", e ); break;
+    }
+    if( (err = fd_long_wait( g, sl )) ) return err;
+    for( unsigned long j=0; j<m; j++ ) memcpy( rq[ i0 + j ].hash, sl->h_dig + 64UL*j, hsz );
+  }
+  if( err ) (void)hipStreamSynchronize( sl->stream );      /* a failed enqueue: what was queued drains before the slot is lent again */
+  fd_ed25519_gpu_unstage( g, vb );
+  return err;
+}
+
+extern "C" int fd_sha512_gpu_long_geometry( unsigned long max_blob, unsigned long max_sigs, unsigned long m,
+                                            unsigned long * G, unsigned long * C ) {
+  fd_sha_long_geom_t geo;
+  int r = fd_sha_long_geom( max_blob, max_sigs, m, FD_SHA_LONG_PINGPONG, &geo );
+  if( G ) *G = geo.G;
+  if( C ) *C = geo.C;
+  return r ? FD_ED25519_ERR_ARG : 0;
 }
 
 /* Pack pointer-array inputs into a pinned slot blob in chunks of the
