@@ -44,6 +44,14 @@ TXN_RESULT_DTYPE = np.dtype([("status", "<i4"), ("sig_base", "<u4"), ("tag", "<u
 _lib = None
 
 
+# fd_poh_gpu_entry_t (fd_poh_gpu.h): one Proof-of-History entry, 112 bytes
+POH_ENTRY_DTYPE = np.dtype([("start", "u1", (32,)), ("mixin", "u1", (32,)), ("expect", "u1", (32,)),
+                            ("n", "<u8"), ("flags", "<u4"), ("_pad", "<u4")])
+POH_MIXIN = 1        # FD_POH_GPU_MIXIN
+POH_ERR_HASH = -1    # FD_POH_ERR_HASH: the chain does not reach expect
+POH_CHUNK_DEFAULT = 16384
+
+
 class Stages:
     """what Engine.debug_stages read back from one launch"""
 
@@ -295,6 +303,26 @@ def lib() -> ctypes.CDLL:
         L.fd_ed25519_gpu_txn_ring_allocs.restype = ul
         L.fd_ed25519_gpu_txn_ring_timed.argtypes = [vp, ul, vp, ul, vp, vp, vp]
         L.fd_ed25519_gpu_txn_ring_timed.restype = ip
+        L.fd_poh_append.argtypes = [vp, ul]
+        L.fd_poh_append.restype = vp
+        L.fd_poh_mixin.argtypes = [vp, vp]
+        L.fd_poh_mixin.restype = vp
+        L.fd_poh_verify_batch.argtypes = [ul, vp, ul, vp, vp, ip]
+        L.fd_poh_verify_batch.restype = ip
+        L.fd_poh_gpu_verify_packed.argtypes = [vp, ul, vp, ul, vp, vp]
+        L.fd_poh_gpu_verify_packed.restype = ip
+        L.fd_poh_gpu_verify_dev.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp]
+        L.fd_poh_gpu_verify_dev.restype = ip
+        L.fd_poh_gpu_work_sz.argtypes = [ul]
+        L.fd_poh_gpu_work_sz.restype = ul
+        L.fd_poh_gpu_chain.argtypes = [ul, vp, vp, vp]
+        L.fd_poh_gpu_chain.restype = None
+        L.fd_poh_gpu_debug_set_chunk.argtypes = [vp, ul]
+        L.fd_poh_gpu_debug_set_chunk.restype = ip
+        L.fd_poh_gpu_debug_set_sort.argtypes = [vp, ip]
+        L.fd_poh_gpu_debug_set_sort.restype = ip
+        L.fd_poh_gpu_chunk.argtypes = [vp]
+        L.fd_poh_gpu_chunk.restype = ul
         _lib = L
     return _lib
 
@@ -733,6 +761,44 @@ class Engine:
             raise EngineError(f"debug_txn_descs: {strerror(err)}: {last_error()}")
         return desc, n_sig.value, res
 
+    def poh_verify(self, entries: np.ndarray, n_max: int, states: bool = False):
+        """fd_poh_gpu_verify_packed: the code of every Proof-of-History entry
+        (0, POH_ERR_HASH, ERR_ARG for an entry the header refuses), lanes
+        ordered by n descending on the device.  states: also each entry's
+        final 32-byte state, as an (n, 32) array."""
+        entries = np.ascontiguousarray(entries, dtype=POH_ENTRY_DTYPE)
+        n = len(entries)
+        out = np.empty(n, dtype=np.int32)
+        st = np.empty((n, 32), dtype=np.uint8) if states else None
+        err = lib().fd_poh_gpu_verify_packed(self._h, n, _p(entries), n_max, _p(out), _p(st) if states else None)
+        if err:
+            raise EngineError(f"poh_verify: {strerror(err)}: {last_error()}")
+        return (out, st) if states else out
+
+    def poh_verify_dev(self, n: int, d_entries: int, n_max: int, d_out: int, d_states: int = 0, d_work: int = 0,
+                       stream: int = 0) -> None:
+        """fd_poh_gpu_verify_dev: device-resident entries in the caller's lane
+        order (raw device pointers; d_work: poh_work_sz(n) bytes); queues the
+        launches and returns."""
+        err = lib().fd_poh_gpu_verify_dev(self._h, n, d_entries, n_max, d_out, d_states or None, d_work or None, stream or None)
+        if err:
+            raise EngineError(f"poh_verify_dev: {strerror(err)}: {last_error()}")
+
+    @property
+    def poh_chunk(self) -> int:
+        """hashes one lane runs per launch (fd_poh_gpu_debug_set_chunk; 0 sets the default)"""
+        return lib().fd_poh_gpu_chunk(self._h)
+
+    @poh_chunk.setter
+    def poh_chunk(self, c: int) -> None:
+        if lib().fd_poh_gpu_debug_set_chunk(self._h, c):
+            raise EngineError(f"poh_chunk: bad chunk {c}")
+
+    def poh_debug_sort(self, on: bool) -> None:
+        """experiments: False keeps the caller's lane order in poh_verify"""
+        if lib().fd_poh_gpu_debug_set_sort(self._h, 1 if on else 0):
+            raise EngineError(f"poh_debug_sort: {last_error()}")
+
     def sha512(self, msgs, is384: bool = False) -> list:
         """SHA-512 (SHA-384) digests of byte strings on the device."""
         n = len(msgs)
@@ -984,6 +1050,58 @@ def verify_batch_single_msg(msg: bytes, sigs: np.ndarray, pubs: np.ndarray) -> t
     out = np.zeros(n, dtype=np.int32)
     r = lib().fd_ed25519_verify_batch_single_msg(m, len(msg), _p(sigs), _p(pubs), n, _p(out))
     return r, out
+
+
+def _poh_state(state: bytes):
+    """a 32-byte state in a 32-aligned buffer (fd_poh_state_t): (keepalive, address)"""
+    if len(state) != 32:
+        raise ValueError("a PoH state is 32 bytes")
+    buf = ctypes.create_string_buffer(64)
+    a = (ctypes.addressof(buf) + 31) & ~31
+    ctypes.memmove(a, bytes(state), 32)
+    return buf, a
+
+
+def poh_append(state: bytes, n: int) -> bytes:
+    """fd_poh_append on the host: n recursive SHA-256 hashes of a 32-byte state"""
+    buf, a = _poh_state(state)
+    lib().fd_poh_append(a, n)
+    return ctypes.string_at(a, 32)
+
+
+def poh_mixin(state: bytes, mixin: bytes) -> bytes:
+    """fd_poh_mixin on the host: SHA-256( state || mixin )"""
+    if len(mixin) != 32:
+        raise ValueError("a PoH mixin is 32 bytes")
+    buf, a = _poh_state(state)
+    lib().fd_poh_mixin(a, bytes(mixin))
+    return ctypes.string_at(a, 32)
+
+
+def poh_verify_batch(entries: np.ndarray, n_max: int, states: bool = False, nthreads: int = 8):
+    """fd_poh_verify_batch: Engine.poh_verify's semantics on host threads"""
+    entries = np.ascontiguousarray(entries, dtype=POH_ENTRY_DTYPE)
+    n = len(entries)
+    out = np.empty(n, dtype=np.int32)
+    st = np.empty((n, 32), dtype=np.uint8) if states else None
+    err = lib().fd_poh_verify_batch(n, _p(entries), n_max, _p(out), _p(st) if states else None, nthreads)
+    if err:
+        raise EngineError(f"poh_verify_batch: {strerror(err)}")
+    return (out, st) if states else out
+
+
+def poh_chain(seed: bytes, hashes: np.ndarray, entries: np.ndarray) -> np.ndarray:
+    """fd_poh_gpu_chain: fill start and expect of consecutive entries (in
+    place) from the hash before the run and the (n, 32) hashes they claim"""
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint8).reshape(-1, 32)
+    if entries.dtype != POH_ENTRY_DTYPE or not entries.flags.c_contiguous or len(entries) != len(hashes) or len(seed) != 32:
+        raise ValueError("poh_chain: contiguous POH_ENTRY_DTYPE entries, one 32-byte hash each, a 32-byte seed")
+    lib().fd_poh_gpu_chain(len(entries), bytes(seed), _p(hashes), _p(entries))
+    return entries
+
+
+def poh_work_sz(n: int) -> int:
+    return lib().fd_poh_gpu_work_sz(n)
 
 
 def txn_claims(blob: np.ndarray, txns: np.ndarray):

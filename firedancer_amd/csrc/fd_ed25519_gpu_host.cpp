@@ -31,6 +31,7 @@
 #include "fd_ed25519_gpu_txn_private.h"
 #include "fd_ed25519_gpu_txn_claim.h"
 #include "fd_sha512_gpu_private.h"
+#include "fd_poh_gpu_private.h"
 
 #define FD_GPU_DEPTH_DEFAULT 3
 #define FD_GPU_DEPTH_MAX     8
@@ -240,14 +241,19 @@ struct fd_ed25519_gpu {
   /* transaction batches on the ring (under the ring lock) */
   unsigned long txn_ring_allocs;  /* slots whose transaction scratch was allocated (fd_ed25519_gpu_txn_ring_allocs) */
   hipEvent_t    txn_ring_ev[4];   /* fd_ed25519_gpu_txn_ring_timed: around the front kernel and the reduce */
+  fd_poh_gpu_ext_t poh;           /* Proof-of-History chains: fd_poh_gpu.cpp's own stream and scratch, made on first use */
   fd_ring_lock  lock;
 };
+
+extern "C" fd_poh_gpu_ext_t * fd_ed25519_gpu_poh_ext( fd_ed25519_gpu_t * g ) { return &g->poh; }
 
 static inline long fd_timeout( fd_ed25519_gpu_t const * g ) { return __atomic_load_n( &g->timeout_ns, __ATOMIC_RELAXED ); }
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if( e_ != hipSuccess ) { fd_gpu_fail( #call, e_ ); goto fail; } } while(0)
 
 extern "C" char const * fd_ed25519_gpu_last_error( void ) { return fd_gpu_err; }
+/* for the host units outside this file (fd_poh_gpu.cpp) */
+extern "C" void fd_ed25519_gpu_set_error( char const * what ) { snprintf( fd_gpu_err, sizeof(fd_gpu_err), "%s", what ); }
 
 extern "C" int fd_ed25519_gpu_device_cnt( void ) {
   int cnt = 0;
@@ -472,6 +478,7 @@ extern "C" void fd_ed25519_gpu_delete( fd_ed25519_gpu_t * g ) {
       return;
     }
   }
+  if( g->poh.fini ) g->poh.fini( g->poh.ctx );
   for( int k=0; k<FD_REG_MAX; k++ ) if( g->reg[k].p ) fd_reg_release( (void *)g->reg[k].p );
   for( int s=0; s<g->depth; s++ ) {
     fd_ed25519_gpu_slot * sl = &g->slot[s];

@@ -1,0 +1,271 @@
+/* fd_poh_gpu.cpp -- host side of the Proof-of-History device path
+   (include/fd_poh_gpu.h; the kernel is fd_k_poh, fd_poh_gpu_kernels.hip).
+
+   It hangs off the engine through one slot (fd_ed25519_gpu_poh_ext): a
+   stream, an event and scratch of its own, made at the first call and
+   freed by fd_ed25519_gpu_delete, so PoH batches neither share nor size
+   the verify path's rings and working sets.
+
+   The packed call orders the lanes by n descending.  Each wave then holds
+   chains of about one length, the long chains start in the first launch,
+   and launch j is given only the prefix of lanes with n > j C: the lanes
+   past it are done and would cost a load each. */
+
+#include <stdio.h>
+#include <string.h>
+#include <time.h>
+#include <algorithm>
+#include <functional>
+#include <mutex>
+#include <vector>
+#include "fd_poh_gpu_private.h"
+
+#define FD_EXPORT extern "C" __attribute__((visibility("default")))
+
+#define FD_POH_N_MAX      0x7fffffffUL   /* entries per call */
+#define FD_POH_CHUNK_MAX  (1UL<<24)
+#define FD_POH_ENT_SZ     sizeof(fd_poh_gpu_entry_t)
+#define FD_POH_ROW_SZ     (4UL*FD_POH_ROW_WORDS)
+
+struct fd_poh_ctx {
+  fd_ed25519_gpu_t * gpu;
+  int           device;
+  std::mutex    lock;        /* one packed call at a time: they share the scratch */
+  hipStream_t   stream;
+  hipEvent_t    done;
+  unsigned long cap;         /* entries the scratch holds */
+  uint8_t *     d_buf;       /* entries | order | codes | states | work rows, each for the call's n rounded up to 4 */
+  uint8_t *     h_in;        /* pinned: entries | order */
+  uint8_t *     h_out;       /* pinned: codes | states */
+  unsigned long chunk;       /* hashes per lane per launch */
+  int           nosort;      /* experiments (fd_poh_gpu_debug_set_sort): the packed call keeps the caller's lane order */
+  int           busy;        /* a call gave up waiting: `done` has not been seen complete since */
+};
+
+static int fd_poh_fail( char const * what, hipError_t e ) {
+  char buf[256];
+  snprintf( buf, sizeof(buf), "%s: %s", what, hipGetErrorString( e ) );
+  fd_ed25519_gpu_set_error( buf );
+  return FD_ED25519_ERR_GPU;
+}
+
+static inline long fd_poh_now_ns( void ) {
+  struct timespec t; clock_gettime( CLOCK_MONOTONIC, &t );
+  return (long)t.tv_sec * 1000000000L + (long)t.tv_nsec;
+}
+
+/* the engine's bounded wait: spin for 20 ms, then a query every ~50 us
+   until the engine's timeout (< 0: none) */
+static int fd_poh_wait( fd_poh_ctx * c ) {
+  long to = fd_ed25519_gpu_timeout( c->gpu ), t0 = fd_poh_now_ns();
+  for(;;) {
+    hipError_t e = hipEventQuery( c->done );
+    if( e == hipSuccess ) return 0;
+    if( e != hipErrorNotReady ) return fd_poh_fail( "hipEventQuery", e );
+    long dt = fd_poh_now_ns() - t0;
+    if( to >= 0 && dt > to ) {
+      char buf[128];
+      snprintf( buf, sizeof(buf), "poh wait: batch not complete after %ld ms", to / 1000000L );
+      fd_ed25519_gpu_set_error( buf );
+      return FD_ED25519_ERR_GPU;
+    }
+    if( dt <= 20000000L ) __builtin_ia32_pause();
+    else { struct timespec ts = { 0, 50000L }; nanosleep( &ts, NULL ); }
+  }
+}
+
+static void fd_poh_free_scratch( fd_poh_ctx * c ) {
+  if( c->d_buf ) hipFree( c->d_buf );
+  if( c->h_in  ) hipHostFree( c->h_in );
+  if( c->h_out ) hipHostFree( c->h_out );
+  c->d_buf = c->h_in = c->h_out = NULL; c->cap = 0UL;
+}
+
+/* fd_ed25519_gpu_delete: the engine's own streams have drained.  If ours
+   does not within the engine's timeout, the scratch is leaked rather than
+   freed under a running kernel. */
+static void fd_poh_fini( void * p ) {
+  fd_poh_ctx * c = (fd_poh_ctx *)p;
+  hipSetDevice( c->device );
+  if( hipEventRecord( c->done, c->stream ) != hipSuccess || fd_poh_wait( c ) ) return;
+  fd_poh_free_scratch( c );
+  hipEventDestroy( c->done );
+  hipStreamDestroy( c->stream );
+  delete c;
+}
+
+static std::mutex fd_poh_make_lock;
+
+static fd_poh_ctx * fd_poh_ctx_get( fd_ed25519_gpu_t * g ) {
+  fd_poh_gpu_ext_t * x = fd_ed25519_gpu_poh_ext( g );
+  std::lock_guard<std::mutex> guard( fd_poh_make_lock );
+  if( x->ctx ) return (fd_poh_ctx *)x->ctx;
+  fd_poh_ctx * c = new fd_poh_ctx();
+  c->gpu = g; c->device = fd_ed25519_gpu_device( g ); c->chunk = FD_POH_GPU_CHUNK_DEFAULT;
+  hipError_t e = hipSetDevice( c->device );
+  if( e == hipSuccess ) e = hipStreamCreateWithFlags( &c->stream, hipStreamNonBlocking );
+  if( e == hipSuccess ) {
+    e = hipEventCreateWithFlags( &c->done, hipEventDisableTiming );
+    if( e != hipSuccess ) hipStreamDestroy( c->stream );
+  }
+  if( e != hipSuccess ) { fd_poh_fail( "poh stream", e ); delete c; return NULL; }
+  x->ctx = c; x->fini = fd_poh_fini;
+  return c;
+}
+
+static inline unsigned long fd_poh_r4( unsigned long n ) { return ( n + 3UL ) & ~3UL; }
+
+static int fd_poh_ensure( fd_poh_ctx * c, unsigned long n4 ) {
+  if( n4 <= c->cap ) return 0;
+  fd_poh_free_scratch( c );
+  unsigned long cap = ( n4 + 1023UL ) & ~1023UL;
+  hipError_t e = hipMalloc( (void **)&c->d_buf, cap * ( FD_POH_ENT_SZ + 4UL + 4UL + 32UL + FD_POH_ROW_SZ ) );
+  if( e == hipSuccess ) e = hipHostMalloc( (void **)&c->h_in,  cap * ( FD_POH_ENT_SZ + 4UL ), hipHostMallocDefault );
+  if( e == hipSuccess ) e = hipHostMalloc( (void **)&c->h_out, cap * ( 4UL + 32UL ),          hipHostMallocDefault );
+  if( e != hipSuccess ) { fd_poh_free_scratch( c ); return fd_poh_fail( "poh scratch", e ); }
+  c->cap = cap;
+  return 0;
+}
+
+static inline int fd_poh_entry_ok( fd_poh_gpu_entry_t const * e, unsigned long n_max ) {
+  return !( e->flags & ~FD_POH_GPU_MIXIN ) && !e->_pad && e->n <= n_max;
+}
+
+/* launches for chains of up to max_n hashes at C per launch: at least one
+   (it writes the codes of the n = 0 and the refused entries) */
+static inline unsigned long fd_poh_launches( unsigned long max_n, unsigned long C ) {
+  unsigned long l = max_n / C + (unsigned long)( max_n % C != 0UL );
+  return l ? l : 1UL;
+}
+
+FD_EXPORT unsigned long fd_poh_gpu_work_sz( unsigned long n ) { return ( n ? n : 1UL ) * FD_POH_ROW_SZ; }
+
+FD_EXPORT int fd_poh_gpu_debug_set_chunk( fd_ed25519_gpu_t * gpu, unsigned long C ) {
+  if( C > FD_POH_CHUNK_MAX ) return FD_ED25519_ERR_ARG;
+  if( !gpu ) gpu = fd_ed25519_gpu_default();
+  if( !gpu ) return FD_ED25519_ERR_GPU;
+  fd_poh_ctx * c = fd_poh_ctx_get( gpu );
+  if( !c ) return FD_ED25519_ERR_GPU;
+  std::lock_guard<std::mutex> guard( c->lock );
+  c->chunk = C ? C : FD_POH_GPU_CHUNK_DEFAULT;
+  return 0;
+}
+
+FD_EXPORT int fd_poh_gpu_debug_set_sort( fd_ed25519_gpu_t * gpu, int on ) {
+  if( !gpu ) gpu = fd_ed25519_gpu_default();
+  if( !gpu ) return FD_ED25519_ERR_GPU;
+  fd_poh_ctx * c = fd_poh_ctx_get( gpu );
+  if( !c ) return FD_ED25519_ERR_GPU;
+  std::lock_guard<std::mutex> guard( c->lock );
+  c->nosort = !on;
+  return 0;
+}
+
+FD_EXPORT unsigned long fd_poh_gpu_chunk( fd_ed25519_gpu_t * gpu ) {
+  if( !gpu ) gpu = fd_ed25519_gpu_default();
+  fd_poh_ctx * c = gpu ? fd_poh_ctx_get( gpu ) : NULL;
+  if( !c ) return 0UL;
+  std::lock_guard<std::mutex> guard( c->lock );
+  return c->chunk;
+}
+
+FD_EXPORT int fd_poh_gpu_verify_packed( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t const * entries,
+                                        unsigned long n_max, int * out, void * state_out_opt ) {
+  if( n > FD_POH_N_MAX || ( n && ( !entries || !out ) ) ) return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  if( !gpu ) gpu = fd_ed25519_gpu_default();
+  if( !gpu ) return FD_ED25519_ERR_GPU;
+  fd_poh_ctx * c = fd_poh_ctx_get( gpu );
+  if( !c ) return FD_ED25519_ERR_GPU;
+  std::lock_guard<std::mutex> guard( c->lock );
+  unsigned long C = c->chunk;
+
+  /* lane order: n descending, entries of one n in the caller's order;
+     refused entries count as n = 0 (the first launch writes their code).
+     Chains below 2^32 hashes sort as one 64-bit key each. */
+  unsigned long max_n = 0UL;
+  for( unsigned long i=0; i<n; i++ ) if( fd_poh_entry_ok( entries + i, n_max ) && entries[i].n > max_n ) max_n = entries[i].n;
+  unsigned long launches = fd_poh_launches( max_n, C );
+  if( launches > FD_POH_GPU_LAUNCH_MAX ) return FD_ED25519_ERR_ARG;
+  std::vector<uint32_t> order( n );
+  std::vector<uint64_t> len( n );       /* len[i]: hashes of lane i */
+  if( c->nosort ) {                     /* the A/B's other side: every launch covers every lane */
+    for( unsigned long i=0; i<n; i++ ) { order[i] = (uint32_t)i; len[i] = max_n; }
+  } else if( max_n <= 0xffffffffUL ) {
+    std::vector<uint64_t> key( n );
+    for( unsigned long i=0; i<n; i++ )
+      key[i] = ( ( fd_poh_entry_ok( entries + i, n_max ) ? entries[i].n : 0UL ) << 32 ) | ( 0xffffffffUL - i );
+    std::sort( key.begin(), key.end(), std::greater<uint64_t>() );
+    for( unsigned long i=0; i<n; i++ ) { order[i] = (uint32_t)( 0xffffffffUL - ( key[i] & 0xffffffffUL ) ); len[i] = key[i] >> 32; }
+  } else {
+    for( unsigned long i=0; i<n; i++ ) order[i] = (uint32_t)i;
+    auto eff = [&]( uint32_t i ) { return fd_poh_entry_ok( entries + i, n_max ) ? entries[i].n : 0UL; };
+    std::stable_sort( order.begin(), order.end(), [&]( uint32_t a, uint32_t b ) { return eff( a ) > eff( b ); } );
+    for( unsigned long i=0; i<n; i++ ) len[i] = eff( order[i] );
+  }
+
+  hipError_t e = hipSetDevice( c->device );
+  if( e != hipSuccess ) return fd_poh_fail( "hipSetDevice", e );
+  if( c->busy ) {                       /* an earlier call's launches may still be using the scratch */
+    if( fd_poh_wait( c ) ) return FD_ED25519_ERR_GPU;
+    c->busy = 0;
+  }
+  unsigned long n4 = fd_poh_r4( n );
+  int err = fd_poh_ensure( c, n4 );
+  if( err ) return err;
+
+  unsigned long in_sz  = n4 * ( FD_POH_ENT_SZ + 4UL );
+  unsigned long out_sz = n4 * ( state_out_opt ? 36UL : 4UL );
+  uint8_t * d_ent   = c->d_buf;
+  uint8_t * d_order = d_ent   + n4 * FD_POH_ENT_SZ;
+  uint8_t * d_out   = d_order + n4 * 4UL;
+  uint8_t * d_state = d_out   + n4 * 4UL;
+  uint8_t * d_work  = d_state + n4 * 32UL;
+  memcpy( c->h_in, entries, n * FD_POH_ENT_SZ );
+  memcpy( c->h_in + n4 * FD_POH_ENT_SZ, order.data(), n * 4UL );
+
+  e = hipMemcpyAsync( d_ent, c->h_in, in_sz, hipMemcpyHostToDevice, c->stream );
+  unsigned long lanes = n;
+  for( unsigned long j=0; j<launches && e == hipSuccess; j++ ) {
+    if( j ) {                           /* the lanes with more than j C hashes */
+      while( lanes && len[lanes-1UL] <= j * C ) lanes--;
+      if( !lanes ) break;
+    }
+    e = fd_poh_gpu_launch( (uint32_t)lanes, j == 0UL, (uint32_t)C, n_max, (fd_poh_gpu_entry_t const *)d_ent, (uint32_t const *)d_order,
+                           (uint32_t *)d_work, (int32_t *)d_out, state_out_opt ? d_state : NULL, c->stream );
+  }
+  if( e == hipSuccess ) e = hipMemcpyAsync( c->h_out, d_out, out_sz, hipMemcpyDeviceToHost, c->stream );
+  /* whatever was queued is waited for, also after a failed enqueue */
+  hipError_t e2 = hipEventRecord( c->done, c->stream );
+  if( e2 != hipSuccess ) { c->busy = 1; return fd_poh_fail( "hipEventRecord", e2 ); }
+  if( fd_poh_wait( c ) ) { c->busy = 1; return FD_ED25519_ERR_GPU; }
+  if( e != hipSuccess ) return fd_poh_fail( "poh launch", e );
+
+  memcpy( out, c->h_out, n * 4UL );
+  if( state_out_opt ) memcpy( state_out_opt, c->h_out + n4 * 4UL, n * 32UL );
+  return 0;
+}
+
+FD_EXPORT int fd_poh_gpu_verify_dev( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t const * d_entries, unsigned long n_max,
+                                     int * d_out, void * d_state_out_opt, void * d_work, void * stream ) {
+  if( n > FD_POH_N_MAX || ( n && ( !d_entries || !d_out || !d_work ) ) ) return FD_ED25519_ERR_ARG;
+  if( ( (uintptr_t)d_work | (uintptr_t)d_state_out_opt ) & 15UL ) return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  if( !gpu ) gpu = fd_ed25519_gpu_default();
+  if( !gpu ) return FD_ED25519_ERR_GPU;
+  fd_poh_ctx * c = fd_poh_ctx_get( gpu );
+  if( !c ) return FD_ED25519_ERR_GPU;
+  unsigned long C;
+  { std::lock_guard<std::mutex> guard( c->lock ); C = c->chunk; }
+  unsigned long launches = fd_poh_launches( n_max, C );
+  if( launches > FD_POH_GPU_LAUNCH_MAX ) return FD_ED25519_ERR_ARG;
+  hipError_t e = hipSetDevice( c->device );
+  if( e != hipSuccess ) return fd_poh_fail( "hipSetDevice", e );
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  for( unsigned long j=0; j<launches; j++ ) {
+    e = fd_poh_gpu_launch( (uint32_t)n, j == 0UL, (uint32_t)C, n_max, d_entries, NULL, (uint32_t *)d_work, (int32_t *)d_out,
+                           (uint8_t *)d_state_out_opt, st );
+    if( e != hipSuccess ) return fd_poh_fail( "poh launch", e );
+  }
+  return 0;
+}
