@@ -761,6 +761,68 @@ static fd_ed25519_gpu_slot * fd_free_slot( fd_ed25519_gpu_t * g, void const * bl
   if( !sl && fd_wait_retiring( g ) ) sl = fd_free_slot_( g, blob );
   return sl;
 }
+
+/* ---- The slot lifecycle of a synchronous call ----------------------------
+
+   take -> stage -> enqueue -> settle, all under g->lock.  The call takes a
+   free slot, stages its input in the slot's pinned blob, queues its own
+   HIP work and the slot's done event on the slot's stream, and hands the
+   outcome to fd_slot_settle, the one way out: no path returns with work
+   queued on a slot that is neither waited for nor orphaned. */
+
+/* Take: the device and a free slot (the staged one owning blob, if any).
+   0, the fd_gpu_fail code, or FD_ED25519_ERR_ARG when every slot is in
+   flight or lent out. */
+static int fd_slot_take( fd_ed25519_gpu_t * g, void const * blob, fd_ed25519_gpu_slot ** sl ) {
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  return (*sl = fd_free_slot( g, blob )) ? 0 : FD_ED25519_ERR_ARG;
+}
+
+/* Stage: the blob into the slot's pinned buffer (unless it is that
+   buffer), zeros up to the 16-aligned offset behind its pad, and the
+   descriptors (or whatever travels in their place) there, so the batch is
+   one H2D copy.  Returns that offset. */
+static unsigned long fd_slot_stage( fd_ed25519_gpu_slot * sl, void const * blob, unsigned long blob_sz, void const * tail, unsigned long tail_sz ) {
+  unsigned long doff = fd_desc_off( blob_sz );
+  if( sl->h_blob != blob ) memcpy( sl->h_blob, blob, blob_sz );
+  memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
+  memcpy( sl->h_blob + doff, tail, tail_sz );
+  return doff;
+}
+
+/* Give up a slot whose done event is queued behind work still in flight:
+   fd_reclaim_orphans brings it back once the event completes. */
+static void fd_slot_orphan( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl ) {
+  sl->ticket = g->next_ticket++; sl->orphan = 1;
+}
+
+/* Settle: the end of every synchronous call (err: what its enqueue on st
+   returned) and of a failed ring enqueue.  Every wait is bounded by the
+   engine's timeout, so a wedged stream never blocks the other users of
+   the engine lock.  An enqueue that went through is waited for; one that
+   failed may have left work on st (the H2D copy from the slot's pinned
+   buffer, kernels on its scratch), which must drain before the slot can be
+   picked again.  A wait that gives up leaves the slot orphaned behind its
+   done event, and a slot that cannot even get that event is never reused
+   (leaked).  Returns the error to hand back. */
+static int fd_slot_settle( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, hipStream_t st, int err ) {
+  if( !err ) {
+    if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) fd_slot_orphan( g, sl );
+  } else if( st && fd_wait_query( fd_stream_query, (void *)st, FD_POLL_SPIN_NS, fd_timeout( g ) ) != 1 ) {
+    /* the slot's done event marks the end of what was queued on st */
+    if( hipEventRecord( sl->done, st ) == hipSuccess ) { fd_slot_orphan( g, sl ); sl->n_txn = 0UL; }
+    else sl->ticket = ~0UL;
+  }
+  return err;
+}
+
+/* Scratch a call allocated for itself, after fd_slot_settle: while the
+   slot is not free again (orphaned or leaked), queued work may still read
+   or write the scratch, host or device, so it is left allocated and never
+   freed -- a leak bounded by the number of timeouts. */
+static inline int fd_slot_in_flight( fd_ed25519_gpu_slot const * sl ) { return sl->ticket != 0UL; }
+
 extern "C" int fd_ed25519_gpu_device( fd_ed25519_gpu_t const * g ) { return g ? g->device : -1; }
 
 extern "C" int fd_ed25519_gpu_slot_states( fd_ed25519_gpu_t * g, int * out, int max ) {
@@ -1016,25 +1078,6 @@ static int fd_ring_busy( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot const * sl ) 
   return 0;
 }
 
-/* On failure, whatever was already queued on the slot's stream (the H2D
-   copy from its pinned buffer, kernels on its scratch) must drain before
-   the slot can be picked again.  The drain is bounded by the engine's
-   timeout like every other wait; a stream that does not drain in time
-   leaves the slot orphaned (reclaimed by fd_free_slot once its event
-   completes) instead of blocking every user of the engine lock. */
-static int fd_slot_enqueue( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n, void const * blob,
-                            unsigned long blob_sz, fd_ed25519_gpu_desc_t const * desc,
-                            void const * blob2 = NULL, unsigned long blob2_sz = 0UL ) {
-  hipStream_t st = NULL;
-  int err = fd_slot_enqueue_( g, sl, n, blob, blob_sz, blob2, blob2_sz, desc, &st );
-  if( err && st && fd_wait_query( fd_stream_query, (void *)st, FD_POLL_SPIN_NS, fd_timeout( g ) ) != 1 ) {
-    /* the slot's done event marks the end of what was queued on st */
-    if( hipEventRecord( sl->done, st ) == hipSuccess ) { sl->ticket = g->next_ticket++; sl->orphan = 1; }
-    else sl->ticket = ~0UL;   /* no event to wait on: never reused (leaked) */
-  }
-  return err;
-}
-
 static void fd_slot_collect( fd_ed25519_gpu_slot * sl, int * out ) {
   memcpy( out, sl->h_out, sl->n * sizeof(int) );
 }
@@ -1044,18 +1087,13 @@ extern "C" int fd_ed25519_gpu_verify_packed( fd_ed25519_gpu_t * g, unsigned long
   if( !g || n > g->max_sigs || blob_sz > g->max_blob || (n && (!desc || !out)) || (blob_sz && !blob) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
   /* use a free slot; synchronous callers serialise on the lock */
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;   /* every slot in flight or lent out */
-  int err = fd_slot_enqueue( g, sl, n, blob, blob_sz, desc );
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, NULL, &sl );
   if( err ) return err;
-  if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) {
-    sl->ticket = g->next_ticket++;   /* still in flight: the slot is not reused until it drains */
-    sl->orphan = 1;
-    return err;
-  }
+  hipStream_t st = NULL;
+  err = fd_slot_enqueue_( g, sl, n, blob, blob_sz, NULL, 0UL, desc, &st );
+  if( (err = fd_slot_settle( g, sl, st, err )) ) return err;
   fd_slot_collect( sl, out );
   return 0;
 }
@@ -1070,7 +1108,9 @@ extern "C" int fd_ed25519_gpu_try_submit2( fd_ed25519_gpu_t * g, unsigned long n
   if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
   fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
   if( !sl ) return 0;                    /* ring full: poll first */
-  int err = fd_slot_enqueue( g, sl, n, blob, blob_sz, desc, blob2, blob2_sz );
+  hipStream_t st = NULL;
+  int err = fd_slot_enqueue_( g, sl, n, blob, blob_sz, blob2, blob2_sz, desc, &st );
+  if( err ) err = fd_slot_settle( g, sl, st, err );
   sl->staged = 0;                        /* released, submitted or not (fd_ed25519_gpu_unstage) */
   if( err ) return err;
   sl->ticket = g->next_ticket++;
@@ -1157,26 +1197,42 @@ extern "C" int fd_ed25519_gpu_debug_fe( fd_ed25519_gpu_t * g, int op, unsigned l
   if( !g || op < 0 || op > 7 || n > (1UL<<20) || (n && (!f || !gg || !h)) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, NULL, &sl );
+  if( err ) return err;
+  hipError_t e;
   hipStream_t st = sl->stream;
   unsigned long sz = 40UL * n;
   int32_t * d = NULL;
-  int err = 0;
   if( (e = hipMalloc( (void **)&d, 5UL * sz )) != hipSuccess ) return fd_gpu_fail( "debug_fe alloc", e );
   if( (e = hipMemcpyAsync( d, f, sz, hipMemcpyHostToDevice, st )) != hipSuccess
    || (e = hipMemcpyAsync( d + 10UL*n, gg, sz, hipMemcpyHostToDevice, st )) != hipSuccess
    || (e = fd_ed25519_gpu_launch_debug_fe( op, n, d, d + 10UL*n, d + 20UL*n, st )) != hipSuccess
    || (e = hipMemcpyAsync( h, d + 20UL*n, 3UL * sz, hipMemcpyDeviceToHost, st )) != hipSuccess
-   || (e = hipEventRecord( sl->done, st )) != hipSuccess ) { err = fd_gpu_fail( "debug_fe", e ); (void)hipStreamSynchronize( st ); }
-  else if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) {
-    sl->ticket = g->next_ticket++; sl->orphan = 1;
-    return err;     /* the buffer may still be in use: leaked */
-  }
-  hipFree( d );
+   || (e = hipEventRecord( sl->done, st )) != hipSuccess ) err = fd_gpu_fail( "debug_fe", e );
+  err = fd_slot_settle( g, sl, st, err );
+  if( !fd_slot_in_flight( sl ) ) hipFree( d );
   return err;
+}
+
+/* n 64-byte digests as the SHA-512 state words fd_k_prep_dig takes: digest
+   byte 8j+b becomes bits 56-8b.. of word j */
+static void fd_dig_words( uint64_t * w, uint8_t const * dig, unsigned long n ) {
+  for( unsigned long i=0; i<8UL*n; i++ ) {
+    uint64_t x = 0UL;
+    for( int b=0; b<8; b++ ) x = (x << 8) | (uint64_t)dig[8UL*i + (unsigned long)b];
+    w[i] = x;
+  }
+}
+
+/* the device's k words [4][n] as n x 32 little-endian bytes: zeros where
+   prep's status is not 1 (no k was computed) */
+static void fd_k_bytes( uint8_t * k_out, uint64_t const * h_k, int32_t const * h_st, unsigned long n ) {
+  for( unsigned long i=0; i<n; i++ )
+    for( int j=0; j<4; j++ ) {
+      uint64_t w = h_st[i] == 1 ? h_k[(unsigned long)j*n + i] : 0UL;
+      for( int b=0; b<8; b++ ) k_out[32UL*i + 8UL*(unsigned long)j + (unsigned long)b] = (uint8_t)(w >> (8*b));
+    }
 }
 
 /* Diagnostics: k = SHA-512(R||A||M) mod L of each signature, computed by
@@ -1197,20 +1253,17 @@ extern "C" int fd_ed25519_gpu_debug_k( fd_ed25519_gpu_t * g, unsigned long n, vo
      on each other's lock */
   std::lock_guard<std::mutex> dguard( g->dev_lock );
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, NULL, &sl );
+  if( err ) return err;
+  hipError_t e;
   hipStream_t st = sl->stream;
-  unsigned long doff = fd_desc_off( blob_sz );
-  memcpy( sl->h_blob, blob, blob_sz );
-  memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
-  memcpy( sl->h_blob + doff, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
+  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
   uint64_t * d_k = (uint64_t *)g->dev_work[0].tab;   /* 1536 B of table scratch per signature >= 32 */
-  uint64_t * h_k = (uint64_t *)malloc( 32UL * n );
-  int32_t * h_st = (int32_t *)malloc( 4UL * n );
-  int err = 0;
-  if( !h_k || !h_st ) { err = FD_ED25519_ERR_GPU; goto done; }
+  uint8_t * h = (uint8_t *)malloc( 36UL * n );       /* k [4][n], status [n] */
+  if( !h ) return FD_ED25519_ERR_GPU;
+  uint64_t * h_k = (uint64_t *)h;
+  int32_t * h_st = (int32_t *)(h + 32UL * n);
   if( (e = fd_dev_serial_begin( g, st )) != hipSuccess
    || (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, doff + n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess
    || (e = hipMemsetAsync( d_k, 0, 32UL * n, st )) != hipSuccess
@@ -1218,19 +1271,20 @@ extern "C" int fd_ed25519_gpu_debug_k( fd_ed25519_gpu_t * g, unsigned long n, vo
    || (e = hipMemcpyAsync( h_k, d_k, 32UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess
    || (e = hipMemcpyAsync( h_st, g->dev_work[0].status, 4UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess
    || (e = hipEventRecord( sl->done, st )) != hipSuccess
-   || (e = fd_dev_serial_end( g, st )) != hipSuccess ) { err = fd_gpu_fail( "debug_k", e ); (void)hipStreamSynchronize( st ); goto done; }
-  if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) { sl->ticket = g->next_ticket++; sl->orphan = 1; goto done; }
-  for( unsigned long i=0; i<n; i++ ) {
-    status_out[i] = h_st[i];
-    for( int j=0; j<4; j++ ) {
-      uint64_t w = h_st[i] == 1 ? h_k[(unsigned long)j*n + i] : 0UL;
-      for( int b=0; b<8; b++ ) k_out[32UL*i + 8UL*(unsigned long)j + (unsigned long)b] = (uint8_t)(w >> (8*b));
-    }
+   || (e = fd_dev_serial_end( g, st )) != hipSuccess ) err = fd_gpu_fail( "debug_k", e );
+  if( err ) (void)fd_dev_serial_end( g, st );   /* best effort: later device-resident launches still wait for what was queued */
+  if( !(err = fd_slot_settle( g, sl, st, err )) ) {
+    memcpy( status_out, h_st, 4UL * n );
+    fd_k_bytes( k_out, h_k, h_st, n );
   }
-done:
-  free( h_k ); free( h_st );
+  if( !fd_slot_in_flight( sl ) ) free( h );
   return err;
 }
+
+static int fd_diag_run( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
+                        fd_ed25519_gpu_desc_t const * desc, uint8_t const * dig, int with_k,
+                        int * codes_out, uint8_t * k_out, int * status_out, int * pstat_out, int * pts_out,
+                        int * op_start_out, uint8_t * ops_out, int * tab_out, int * fin_out, int * info_out );
 
 /* Diagnostics: the verify pipeline with each signature's 64-byte digest
    given by the caller (dig, n x 64 bytes: what the reference hands to
@@ -1250,72 +1304,7 @@ extern "C" int fd_ed25519_gpu_debug_verify_dig( fd_ed25519_gpu_t * g, unsigned l
   if( !g || n > g->max_sigs || blob_sz > g->max_blob || (n && (!desc || !dig || !codes_out)) || (blob_sz && !blob) )
     return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
-  fd_knobs kn = fd_knobs_get( g );     /* before the locks below: fd_knobs_get takes g->lock itself */
-  /* both engine locks, dev_lock first (fd_ed25519_gpu_debug_k) */
-  std::lock_guard<std::mutex> dguard( g->dev_lock );
-  std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;
-  hipStream_t st = sl->stream;
-  unsigned long doff = fd_desc_off( blob_sz );
-  memcpy( sl->h_blob, blob, blob_sz );
-  memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
-  memcpy( sl->h_blob + doff, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
-  fd_ed25519_gpu_desc_t const * d_desc = (fd_ed25519_gpu_desc_t const *)(sl->d_blob + doff);
-  fd_ed25519_gpu_work_t const * w = &g->dev_work[0];
-  /* host and device scratch: state words [n][8], k [4][n], codes [n] (the
-     working set's table scratch is the DSM's here) */
-  unsigned long const o_k = 64UL * n, o_c = 96UL * n, sz = 100UL * n, o_st = sz;   /* the host copy holds prep's status too */
-  uint8_t * h = (uint8_t *)malloc( sz + 4UL * n );
-  uint8_t * d = NULL;
-  int err = 0;
-  if( !h ) return FD_ED25519_ERR_GPU;
-  if( (e = hipMalloc( (void **)&d, sz )) != hipSuccess ) { free( h ); return fd_gpu_fail( "debug_verify_dig alloc", e ); }
-  {
-    uint64_t * hw = (uint64_t *)h;
-    for( unsigned long i=0; i<8UL*n; i++ ) {
-      uint64_t x = 0UL;
-      for( int b=0; b<8; b++ ) x = (x << 8) | (uint64_t)dig[8UL*i + (unsigned long)b];
-      hw[i] = x;
-    }
-  }
-  if( (e = fd_dev_serial_begin( g, st )) != hipSuccess
-   || (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, doff + n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess
-   || (e = hipMemcpyAsync( d, h, 64UL * n, hipMemcpyHostToDevice, st )) != hipSuccess
-   || (e = hipMemsetAsync( d + o_k, 0, 32UL * n, st )) != hipSuccess
-   || (e = hipMemsetAsync( d + o_c, 0x7f, 4UL * n, st )) != hipSuccess       /* no code: a row the DSM left unwritten shows */
-   || (e = fd_ed25519_gpu_launch_front_dig( n, sl->d_blob, blob_sz, d_desc, (uint64_t const *)d, w, (uint64_t *)(d + o_k), st,
-                                            kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )) != hipSuccess
-   || (e = hipMemcpyAsync( h + o_st, w->status, 4UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess   /* prep's, before the DSM settles it */
-   || (e = fd_ed25519_gpu_launch_back( n, sl->d_blob, d_desc, w, (int32_t *)(d + o_c), st, NULL,
-                                       kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )) != hipSuccess
-   || (e = hipMemcpyAsync( h + o_k, d + o_k, 36UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess
-   || (e = hipEventRecord( sl->done, st )) != hipSuccess
-   || (e = fd_dev_serial_end( g, st )) != hipSuccess ) { err = fd_gpu_fail( "debug_verify_dig", e ); (void)hipStreamSynchronize( st ); goto done; }
-  if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) {
-    sl->ticket = g->next_ticket++; sl->orphan = 1;
-    free( h );
-    return err;     /* the device buffer may still be in use: leaked */
-  }
-  {
-    int32_t const *  h_st = (int32_t const *)(h + o_st);
-    uint64_t const * h_k  = (uint64_t const *)(h + o_k);
-    memcpy( codes_out, h + o_c, 4UL * n );
-    for( unsigned long i=0; i<n; i++ ) {
-      if( status_out ) status_out[i] = h_st[i];
-      if( k_out )
-        for( int j=0; j<4; j++ ) {
-          uint64_t x = h_st[i] == 1 ? h_k[(unsigned long)j*n + i] : 0UL;
-          for( int b=0; b<8; b++ ) k_out[32UL*i + 8UL*(unsigned long)j + (unsigned long)b] = (uint8_t)(x >> (8*b));
-        }
-    }
-  }
-done:
-  hipFree( d );
-  free( h );
-  return err;
+  return fd_diag_run( g, n, blob, blob_sz, desc, dig, 1, codes_out, k_out, status_out, NULL, NULL, NULL, NULL, NULL, NULL, NULL );
 }
 
 /* Diagnostics: one verify launch with the stages it leaves in the working
@@ -1333,6 +1322,18 @@ extern "C" int fd_ed25519_gpu_debug_stages( fd_ed25519_gpu_t * g, unsigned long 
                                             int * info_out ) {
   if( !g || n > g->max_sigs || blob_sz > g->max_blob || (n && !desc) || (blob_sz && !blob) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
+  return fd_diag_run( g, n, blob, blob_sz, desc, dig, 0, codes_out, NULL, status_out, pstat_out, pts_out, op_start_out, ops_out,
+                      tab_out, fin_out, info_out );
+}
+
+/* The core of the two: take, stage, one serial launch on dev_work[0] with
+   scratch of its own, settle, unpack.  with_k (dig given): fd_k_prep_dig
+   also leaves k, which k_out (if not NULL) receives as
+   fd_ed25519_gpu_debug_k's.  Every out pointer may be NULL. */
+static int fd_diag_run( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
+                        fd_ed25519_gpu_desc_t const * desc, uint8_t const * dig, int with_k,
+                        int * codes_out, uint8_t * k_out, int * status_out, int * pstat_out, int * pts_out,
+                        int * op_start_out, uint8_t * ops_out, int * tab_out, int * fin_out, int * info_out ) {
   fd_knobs kn = fd_knobs_get( g );     /* before the locks below: fd_knobs_get takes g->lock itself */
   /* the schedule, by fd_ed25519_gpu_launch_front's and _back's predicates */
   int const portable = (kn.mode & 0xff) == FD_ED25519_GPU_MODE_PORTABLE;
@@ -1346,20 +1347,18 @@ extern "C" int fd_ed25519_gpu_debug_stages( fd_ed25519_gpu_t * g, unsigned long 
   /* both engine locks, dev_lock first (fd_ed25519_gpu_debug_k) */
   std::lock_guard<std::mutex> dguard( g->dev_lock );
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, NULL, &sl );
+  if( err ) return err;
+  hipError_t e;
   hipStream_t st = sl->stream;
-  unsigned long doff = fd_desc_off( blob_sz );
-  memcpy( sl->h_blob, blob, blob_sz );
-  memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
-  memcpy( sl->h_blob + doff, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
+  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
   fd_ed25519_gpu_desc_t const * d_desc = (fd_ed25519_gpu_desc_t const *)(sl->d_blob + doff);
   fd_ed25519_gpu_work_t const * w = &g->dev_work[0];
-  /* device scratch: state words [n][8], codes [n]; the host copy holds the
+  /* device scratch: state words [n][8], k [4][n] (with_k), codes [n] (the
+     working set's table scratch is the DSM's here); the host copy holds the
      stages behind them, each only if asked for */
-  unsigned long const o_c = 64UL * n, dsz = 68UL * n;
+  unsigned long const o_k = 64UL * n, o_c = o_k + ( with_k ? 32UL * n : 0UL ), dsz = o_c + 4UL * n;
   unsigned long o = dsz;
   unsigned long const o_st  = o; o += 4UL * n;
   unsigned long const o_ps  = o; o += pstat_out    ? 8UL * n : 0UL;
@@ -1370,29 +1369,23 @@ extern "C" int fd_ed25519_gpu_debug_stages( fd_ed25519_gpu_t * g, unsigned long 
   unsigned long const o_tab = o; o += tab_out && has_tab ? 4UL * (unsigned long)FD_TAB_SIG * n : 0UL;
   uint8_t * h = (uint8_t *)malloc( o );
   uint8_t * d = NULL;
-  int err = 0;
   if( !h ) return FD_ED25519_ERR_GPU;
   if( (e = hipMalloc( (void **)&d, dsz )) != hipSuccess ) { free( h ); return fd_gpu_fail( "debug_stages alloc", e ); }
-  if( dig ) {
-    uint64_t * hw = (uint64_t *)h;
-    for( unsigned long i=0; i<8UL*n; i++ ) {
-      uint64_t x = 0UL;
-      for( int b=0; b<8; b++ ) x = (x << 8) | (uint64_t)dig[8UL*i + (unsigned long)b];
-      hw[i] = x;
-    }
-  }
+  if( dig ) fd_dig_words( (uint64_t *)h, dig, n );
   if( (e = fd_dev_serial_begin( g, st )) != hipSuccess
    || (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, doff + n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess
    || (dig && (e = hipMemcpyAsync( d, h, 64UL * n, hipMemcpyHostToDevice, st )) != hipSuccess)
+   || (with_k && (e = hipMemsetAsync( d + o_k, 0, 32UL * n, st )) != hipSuccess)
    || (e = hipMemsetAsync( d + o_c, 0x7f, 4UL * n, st )) != hipSuccess       /* no code: a row the DSM left unwritten shows */
-   || (e = dig ? fd_ed25519_gpu_launch_front_dig( n, sl->d_blob, blob_sz, d_desc, (uint64_t const *)d, w, (uint64_t *)NULL, st,
+   || (e = dig ? fd_ed25519_gpu_launch_front_dig( n, sl->d_blob, blob_sz, d_desc, (uint64_t const *)d, w,
+                                                  with_k ? (uint64_t *)(d + o_k) : (uint64_t *)NULL, st,
                                                   kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )
                : fd_ed25519_gpu_launch_front( n, sl->d_blob, blob_sz, d_desc, w, st, NULL,
                                               kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )) != hipSuccess
    || (e = hipMemcpyAsync( h + o_st, w->status, 4UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess   /* prep's, before the DSM settles it */
    || (e = fd_ed25519_gpu_launch_back( n, sl->d_blob, d_desc, w, (int32_t *)(d + o_c), st, NULL,
                                        kn.mode, kn.pool_min, kn.quad_max, kn.oct_max )) != hipSuccess
-   || (e = hipMemcpyAsync( h + o_c, d + o_c, 4UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess
+   || (e = hipMemcpyAsync( h + o_k, d + o_k, dsz - o_k, hipMemcpyDeviceToHost, st )) != hipSuccess   /* k (with_k) and the codes */
    || (pstat_out    && (e = hipMemcpyAsync( h + o_ps,  w->pstat,    8UL * n,   hipMemcpyDeviceToHost, st )) != hipSuccess)
    || (op_start_out && (e = hipMemcpyAsync( h + o_os,  w->op_start, 4UL * n,   hipMemcpyDeviceToHost, st )) != hipSuccess)
    || (pts_out      && (e = hipMemcpyAsync( h + o_pts, w->pts,      320UL * n, hipMemcpyDeviceToHost, st )) != hipSuccess)
@@ -1400,14 +1393,15 @@ extern "C" int fd_ed25519_gpu_debug_stages( fd_ed25519_gpu_t * g, unsigned long 
    || (ops_out      && (e = hipMemcpyAsync( h + o_ops, w->ops, (unsigned long)FD_OPS_MAX * n, hipMemcpyDeviceToHost, st )) != hipSuccess)
    || (o != o_tab   && (e = hipMemcpyAsync( h + o_tab, w->tab, 4UL * (unsigned long)FD_TAB_SIG * n, hipMemcpyDeviceToHost, st )) != hipSuccess)
    || (e = hipEventRecord( sl->done, st )) != hipSuccess
-   || (e = fd_dev_serial_end( g, st )) != hipSuccess ) { err = fd_gpu_fail( "debug_stages", e ); (void)hipStreamSynchronize( st ); goto done; }
-  if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) {
-    sl->ticket = g->next_ticket++; sl->orphan = 1;
-    free( h );
-    return err;     /* the device buffer may still be in use: leaked */
+   || (e = fd_dev_serial_end( g, st )) != hipSuccess ) err = fd_gpu_fail( "debug_stages", e );
+  if( err ) (void)fd_dev_serial_end( g, st );   /* as fd_ed25519_gpu_debug_k */
+  if( (err = fd_slot_settle( g, sl, st, err )) ) {
+    if( !fd_slot_in_flight( sl ) ) { hipFree( d ); free( h ); }
+    return err;
   }
   if( codes_out )    memcpy( codes_out,    h + o_c,  4UL * n );
   if( status_out )   memcpy( status_out,   h + o_st, 4UL * n );
+  if( k_out )        fd_k_bytes( k_out, (uint64_t const *)(h + o_k), (int32_t const *)(h + o_st), n );
   if( pstat_out )    memcpy( pstat_out,    h + o_ps, 8UL * n );
   if( op_start_out ) memcpy( op_start_out, h + o_os, 4UL * n );
   if( pts_out ) {      /* device: [40][2n] -> [2n][40] */
@@ -1433,10 +1427,9 @@ extern "C" int fd_ed25519_gpu_debug_stages( fd_ed25519_gpu_t * g, unsigned long 
   }
   if( fin_out && pooled ) memcpy( fin_out, h + o_fin, 160UL * n );
   if( info_out ) { info_out[0] = sched; info_out[1] = sigmajor; info_out[2] = has_tab; info_out[3] = pooled; }
-done:
   hipFree( d );
   free( h );
-  return err;
+  return 0;
 }
 
 /* SHA-512 / SHA-384 of n messages blob[msg_off..+msg_sz) (sig_off and
@@ -1449,27 +1442,23 @@ extern "C" int fd_ed25519_gpu_sha512_packed( fd_ed25519_gpu_t * g, unsigned long
   for( unsigned long i=0; i<n; i++ )
     if( (unsigned long)desc[i].msg_off + (unsigned long)desc[i].msg_sz > blob_sz ) return FD_ED25519_ERR_ARG;
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
-  if( !sl ) return FD_ED25519_ERR_ARG;
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, blob, &sl );
+  if( err ) return err;
+  hipError_t e;
+  hipStream_t st = sl->stream;
   if( !sl->h_dig && (e = hipHostMalloc( (void **)&sl->h_dig, g->max_sigs * 64UL, hipHostMallocDefault )) != hipSuccess )
     return fd_gpu_fail( "hipHostMalloc digests", e );
   if( sl->h_blob != blob ) memcpy( sl->h_blob, blob, blob_sz );
   memset( sl->h_blob + blob_sz, 0, FD_BLOB_PAD );
   if( sl->h_desc != desc ) memcpy( sl->h_desc, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
   void * d_dig = sl->work.tab;   /* 1536 B per signature of scratch >= 64 B per message */
-  if( (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, blob_sz + FD_BLOB_PAD, hipMemcpyHostToDevice, sl->stream )) != hipSuccess )
-    return fd_gpu_fail( "H2D blob", e );
-  if( (e = hipMemcpyAsync( sl->d_desc, sl->h_desc, n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, sl->stream )) != hipSuccess )
-    return fd_gpu_fail( "H2D desc", e );
-  if( (e = fd_ed25519_gpu_launch_sha512( n, sl->d_blob, sl->d_desc, d_dig, is384, sl->stream )) != hipSuccess )
-    return fd_gpu_fail( "launch sha512", e );
-  if( (e = hipMemcpyAsync( sl->h_dig, d_dig, n * 64UL, hipMemcpyDeviceToHost, sl->stream )) != hipSuccess )
-    return fd_gpu_fail( "D2H digests", e );
-  if( (e = hipEventRecord( sl->done, sl->stream )) != hipSuccess ) return fd_gpu_fail( "event", e );
-  int err = fd_event_wait( sl->done, fd_timeout( g ) );
-  if( err ) { sl->ticket = g->next_ticket++; sl->orphan = 1; return err; }
+  if(      (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, blob_sz + FD_BLOB_PAD, hipMemcpyHostToDevice, st )) != hipSuccess ) err = fd_gpu_fail( "H2D blob", e );
+  else if( (e = hipMemcpyAsync( sl->d_desc, sl->h_desc, n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess ) err = fd_gpu_fail( "H2D desc", e );
+  else if( (e = fd_ed25519_gpu_launch_sha512( n, sl->d_blob, sl->d_desc, d_dig, is384, st )) != hipSuccess ) err = fd_gpu_fail( "launch sha512", e );
+  else if( (e = hipMemcpyAsync( sl->h_dig, d_dig, n * 64UL, hipMemcpyDeviceToHost, st )) != hipSuccess ) err = fd_gpu_fail( "D2H digests", e );
+  else if( (e = hipEventRecord( sl->done, st )) != hipSuccess ) err = fd_gpu_fail( "event", e );
+  if( (err = fd_slot_settle( g, sl, st, err )) ) return err;
   unsigned long hsz = is384 ? 48UL : 64UL;
   for( unsigned long i=0; i<n; i++ ) memcpy( (uint8_t *)hash_out + i*hsz, sl->h_dig + i*64UL, hsz );
   sl->staged = 0;
@@ -1601,7 +1590,7 @@ static int fd_long_wait( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl ) {
   int err = fd_event_wait( sl->done, fd_timeout( g ) );
   if( err ) {
     std::lock_guard<fd_ring_lock> guard( g->lock );
-    sl->ticket = g->next_ticket++; sl->orphan = 1; sl->staged = 0;
+    fd_slot_orphan( g, sl ); sl->staged = 0;
   }
   return err;
 }
@@ -1692,7 +1681,7 @@ static int fd_sha_half_wait( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, hip
   int err = fd_event_wait( ev, fd_timeout( g ) );
   if( err && hipEventRecord( sl->done, sl->stream ) == hipSuccess ) {
     std::lock_guard<fd_ring_lock> guard( g->lock );
-    sl->ticket = g->next_ticket++; sl->orphan = 1; sl->staged = 0;
+    fd_slot_orphan( g, sl ); sl->staged = 0;
   }
   return err;
 }
@@ -2008,24 +1997,20 @@ static int fd_sgn_run( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned 
     memset( sl->h_blob, 0, clear_sz );
     return fd_gpu_fail( "hipHostMalloc signing results", e );
   }
-  if( (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, in_sz, hipMemcpyHostToDevice, st )) != hipSuccess ) { err = fd_gpu_fail( "H2D signing batch", e ); goto drain; }
-  if( sign ) e = fd_ed25519_gpu_launch_sign( n, sl->d_blob, blob_sz, (fd_ed25519_gpu_sign_desc_t const *)(sl->d_blob + doff),
-                                             d_res, d_res + 64UL*n, (int32_t *)(d_res + 96UL*n), binv, st );
-  else       e = fd_ed25519_gpu_launch_public( n, sl->d_blob, d_res, 1, binv, st );
-  if( e != hipSuccess ) { err = fd_gpu_fail( "launch sign", e ); goto drain; }
-  if( (e = hipMemcpyAsync( sl->h_sgn, d_res, res_sz, hipMemcpyDeviceToHost, st )) != hipSuccess ) { err = fd_gpu_fail( "D2H signatures", e ); goto drain; }
-  if( (e = hipMemsetAsync( sl->d_blob, 0, clear_sz, st )) != hipSuccess ) { err = fd_gpu_fail( "clear seeds", e ); goto drain; }
-  if( (e = hipEventRecord( sl->done, st )) != hipSuccess ) { err = fd_gpu_fail( "event", e ); goto drain; }
-  err = fd_event_wait( sl->done, fd_timeout( g ) );
-  if( err ) { sl->ticket = g->next_ticket++; sl->orphan = 1; }   /* the stream still clears the device blob before the slot comes back */
-  memset( sl->h_blob, 0, clear_sz );
-  return err;
-drain:
-  /* part of the batch may be queued: let it finish, then clear both copies */
-  (void)hipStreamSynchronize( st );
-  (void)hipMemsetAsync( sl->d_blob, 0, clear_sz, st );
-  (void)hipStreamSynchronize( st );
-  (void)hipGetLastError();
+  if( (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, in_sz, hipMemcpyHostToDevice, st )) != hipSuccess ) err = fd_gpu_fail( "H2D signing batch", e );
+  else if( (e = sign ? fd_ed25519_gpu_launch_sign( n, sl->d_blob, blob_sz, (fd_ed25519_gpu_sign_desc_t const *)(sl->d_blob + doff),
+                                                   d_res, d_res + 64UL*n, (int32_t *)(d_res + 96UL*n), binv, st )
+                     : fd_ed25519_gpu_launch_public( n, sl->d_blob, d_res, 1, binv, st )) != hipSuccess ) err = fd_gpu_fail( "launch sign", e );
+  else if( (e = hipMemcpyAsync( sl->h_sgn, d_res, res_sz, hipMemcpyDeviceToHost, st )) != hipSuccess ) err = fd_gpu_fail( "D2H signatures", e );
+  else if( (e = hipMemsetAsync( sl->d_blob, 0, clear_sz, st )) != hipSuccess ) err = fd_gpu_fail( "clear seeds", e );
+  else if( (e = hipEventRecord( sl->done, st )) != hipSuccess ) err = fd_gpu_fail( "event", e );
+  if( err ) {
+    /* part of the batch may be queued: the clear goes behind it (best effort) */
+    (void)hipMemsetAsync( sl->d_blob, 0, clear_sz, st );
+    (void)hipGetLastError();
+  }
+  /* a slot orphaned here still has the clear on its stream ahead of its done event */
+  err = fd_slot_settle( g, sl, st, err );
   memset( sl->h_blob, 0, clear_sz );
   return err;
 }
@@ -2035,16 +2020,11 @@ extern "C" int fd_ed25519_gpu_sign_packed( fd_ed25519_gpu_t * g, unsigned long n
   if( !g || n > g->max_sigs || blob_sz > g->max_blob || (n && (!sdesc || !sig_out || !out)) || (blob_sz && !blob) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
-  if( !sl ) return FD_ED25519_ERR_ARG;
-  unsigned long doff = fd_desc_off( blob_sz );
-  if( sl->h_blob != blob ) memcpy( sl->h_blob, blob, blob_sz );
-  memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
-  memcpy( sl->h_blob + doff, sdesc, n * sizeof(fd_ed25519_gpu_sign_desc_t) );
-  int err = fd_sgn_run( g, sl, n, doff + n * sizeof(fd_ed25519_gpu_sign_desc_t), blob_sz, blob_sz, doff, 1 );
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, blob, &sl );
   if( err ) return err;
+  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, sdesc, n * sizeof(fd_ed25519_gpu_sign_desc_t) );
+  if( (err = fd_sgn_run( g, sl, n, doff + n * sizeof(fd_ed25519_gpu_sign_desc_t), blob_sz, blob_sz, doff, 1 )) ) return err;
   memcpy( sig_out, sl->h_sgn, 64UL*n );
   if( pub_out_opt ) memcpy( pub_out_opt, sl->h_sgn + 64UL*n, 32UL*n );
   memcpy( out, sl->h_sgn + 96UL*n, 4UL*n );
@@ -2056,13 +2036,11 @@ extern "C" int fd_ed25519_gpu_public_packed( fd_ed25519_gpu_t * g, unsigned long
   if( !g || n > g->max_sigs || 32UL*n > g->blob_cap || (n && (!seeds || !pub_out)) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;
-  memcpy( sl->h_blob, seeds, 32UL*n );
-  int err = fd_sgn_run( g, sl, n, 32UL*n, 32UL*n, 0UL, 0UL, 0 );
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, NULL, &sl );
   if( err ) return err;
+  memcpy( sl->h_blob, seeds, 32UL*n );
+  if( (err = fd_sgn_run( g, sl, n, 32UL*n, 32UL*n, 0UL, 0UL, 0 )) ) return err;
   memcpy( pub_out, sl->h_sgn, 32UL*n );
   return 0;
 }
@@ -2087,14 +2065,13 @@ extern "C" int fd_ed25519_gpu_debug_sign_op( fd_ed25519_gpu_t * g, int op, unsig
   if( !g || op < 0 || op > 1 || n > (1UL<<20) || (n && (!in0 || !out || (op == 1 && (!in1 || !in2)))) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, NULL, &sl );
+  if( err ) return err;
+  hipError_t e;
   hipStream_t st = sl->stream;
   unsigned long sz = 32UL * n;
   uint8_t * d = NULL;
-  int err = 0;
   if( (e = hipMalloc( (void **)&d, 4UL * sz )) != hipSuccess ) return fd_gpu_fail( "debug_sign_op alloc", e );
   if( (e = hipMemcpyAsync( d, in0, sz, hipMemcpyHostToDevice, st )) != hipSuccess
    || ( op == 1 && ( (e = hipMemcpyAsync( d + sz, in1, sz, hipMemcpyHostToDevice, st )) != hipSuccess
@@ -2102,12 +2079,9 @@ extern "C" int fd_ed25519_gpu_debug_sign_op( fd_ed25519_gpu_t * g, int op, unsig
    || (e = ( op == 0 ? fd_ed25519_gpu_launch_public( n, d, d + 3UL*sz, 0, __atomic_load_n( &fd_sgn_batch_inv, __ATOMIC_RELAXED ), st )
                      : fd_ed25519_gpu_launch_debug_muladd( n, d, d + sz, d + 2UL*sz, d + 3UL*sz, st ) )) != hipSuccess
    || (e = hipMemcpyAsync( out, d + 3UL*sz, sz, hipMemcpyDeviceToHost, st )) != hipSuccess
-   || (e = hipEventRecord( sl->done, st )) != hipSuccess ) { err = fd_gpu_fail( "debug_sign_op", e ); (void)hipStreamSynchronize( st ); }
-  else if( (err = fd_event_wait( sl->done, fd_timeout( g ) )) ) {
-    sl->ticket = g->next_ticket++; sl->orphan = 1;
-    return err;     /* the buffer may still be in use: leaked */
-  }
-  hipFree( d );
+   || (e = hipEventRecord( sl->done, st )) != hipSuccess ) err = fd_gpu_fail( "debug_sign_op", e );
+  err = fd_slot_settle( g, sl, st, err );
+  if( !fd_slot_in_flight( sl ) ) hipFree( d );
   return err;
 }
 
@@ -2338,49 +2312,44 @@ extern "C" int fd_ed25519_gpu_verify_txns_dev_timed( fd_ed25519_gpu_t * g, unsig
 /* One launch of a host-buffer call on slot sl, whose device blob holds the
    batch: entries txn[0, nt) in, results, n_sig, codes (verify) or
    descriptors, and fd_txn_t rows out, all through the staging; waits for
-   it.  Caller holds both engine locks. */
+   it (fd_slot_settle: the blob copy fd_txn_blob_in queued is on the same
+   stream).  Caller holds both engine locks. */
 static int fd_txn_host_run( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long blob_sz, fd_ed25519_gpu_txn_t const * txn,
                             unsigned long nt, unsigned long cap, unsigned long stride, fd_knobs const & kn, int verify ) {
   hipError_t e;
   hipStream_t st = sl->stream;
-  int err = fd_txn_ensure( g, nt, nt * stride );
-  if( err ) return err;
-  fd_txn_pk_off o = fd_txn_pk_layout( g->txn_cap, g->max_sigs );
-  uint8_t * d = g->d_txn_pk, * h = g->h_txn_pk;
-  memcpy( h + o.txn, txn, nt * sizeof(fd_ed25519_gpu_txn_t) );
-  if( (e = hipMemcpyAsync( d + o.txn, h + o.txn, nt * sizeof(fd_ed25519_gpu_txn_t), hipMemcpyHostToDevice, st )) != hipSuccess ) {
-    err = fd_gpu_fail( "H2D transactions", e ); goto drain;
-  }
-  int b;
-  if( (err = fd_txn_dev_run( g, nt, sl->d_blob, blob_sz, (fd_ed25519_gpu_txn_t const *)(d + o.txn), cap,
-                             (fd_ed25519_gpu_txn_result_t *)(d + o.res), NULL, stride ? d + o.out : NULL, stride, st, kn, verify, NULL, &b )) )
-    goto drain;
-  {
+  int err;
+  do {
+    if( (err = fd_txn_ensure( g, nt, nt * stride )) ) break;
+    fd_txn_pk_off o = fd_txn_pk_layout( g->txn_cap, g->max_sigs );
+    uint8_t * d = g->d_txn_pk, * h = g->h_txn_pk;
+    memcpy( h + o.txn, txn, nt * sizeof(fd_ed25519_gpu_txn_t) );
+    if( (e = hipMemcpyAsync( d + o.txn, h + o.txn, nt * sizeof(fd_ed25519_gpu_txn_t), hipMemcpyHostToDevice, st )) != hipSuccess ) {
+      err = fd_gpu_fail( "H2D transactions", e ); break;
+    }
+    int b;
+    if( (err = fd_txn_dev_run( g, nt, sl->d_blob, blob_sz, (fd_ed25519_gpu_txn_t const *)(d + o.txn), cap,
+                               (fd_ed25519_gpu_txn_result_t *)(d + o.res), NULL, stride ? d + o.out : NULL, stride, st, kn, verify, NULL, &b )) )
+      break;
     fd_txn_set * ts = &g->txn_set[b];
     unsigned long per = verify ? sizeof(int32_t) : sizeof(fd_ed25519_gpu_desc_t);
     if( (e = hipMemcpyAsync( h + o.res, d + o.res, nt * sizeof(fd_ed25519_gpu_txn_result_t), hipMemcpyDeviceToHost, st )) != hipSuccess
      || (e = hipMemcpyAsync( h + o.nsig, ts->part + fd_txn_part_cnt( nt ) - 1UL, sizeof(uint32_t), hipMemcpyDeviceToHost, st )) != hipSuccess
      || ( cap && (e = hipMemcpyAsync( h + o.sig, verify ? (void const *)ts->codes : (void const *)ts->desc, cap * per, hipMemcpyDeviceToHost, st )) != hipSuccess )
      || ( stride && (e = hipMemcpyAsync( h + o.out, d + o.out, nt * stride, hipMemcpyDeviceToHost, st )) != hipSuccess )
-     || (e = hipEventRecord( sl->done, st )) != hipSuccess ) { err = fd_gpu_fail( "D2H transactions", e ); goto drain; }
-  }
-  err = fd_event_wait( sl->done, fd_timeout( g ) );
-  if( err ) { sl->ticket = g->next_ticket++; sl->orphan = 1; }
-  return err;
-drain:
-  (void)hipStreamSynchronize( st );
-  (void)hipGetLastError();
-  return err;
+     || (e = hipEventRecord( sl->done, st )) != hipSuccess ) err = fd_gpu_fail( "D2H transactions", e );
+  } while(0);
+  if( err ) (void)hipGetLastError();
+  return fd_slot_settle( g, sl, st, err );
 }
 
 /* the batch's bytes into slot sl's device blob (with the pad the kernels
-   may read past blob_sz) */
+   may read past blob_sz); the caller settles a failure */
 static int fd_txn_blob_in( fd_ed25519_gpu_slot * sl, void const * blob, unsigned long blob_sz ) {
   if( blob_sz ) memcpy( sl->h_blob, blob, blob_sz );
   memset( sl->h_blob + blob_sz, 0, FD_BLOB_PAD );
   hipError_t e = hipMemcpyAsync( sl->d_blob, sl->h_blob, blob_sz + FD_BLOB_PAD, hipMemcpyHostToDevice, sl->stream );
-  if( e != hipSuccess ) { (void)hipStreamSynchronize( sl->stream ); return fd_gpu_fail( "H2D transaction blob", e ); }
-  return 0;
+  return e == hipSuccess ? 0 : fd_gpu_fail( "H2D transaction blob", e );
 }
 
 extern "C" int fd_ed25519_gpu_verify_txns_packed( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
@@ -2396,12 +2365,10 @@ extern "C" int fd_ed25519_gpu_verify_txns_packed( fd_ed25519_gpu_t * g, unsigned
   /* both engine locks, dev_lock first, as fd_ed25519_gpu_debug_k */
   std::lock_guard<std::mutex> dguard( g->dev_lock );
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;
-  int err = fd_txn_blob_in( sl, blob, blob_sz );
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, NULL, &sl );
   if( err ) return err;
+  if( (err = fd_txn_blob_in( sl, blob, blob_sz )) ) return fd_slot_settle( g, sl, sl->stream, err );
   /* nothing is written on failure: everything lands in these first */
   std::vector<fd_ed25519_gpu_txn_result_t> hres( n_txn );
   std::vector<int32_t> hcodes;
@@ -2446,12 +2413,10 @@ extern "C" int fd_ed25519_gpu_debug_txn_descs( fd_ed25519_gpu_t * g, unsigned lo
   fd_knobs kn = fd_knobs_get( g );
   std::lock_guard<std::mutex> dguard( g->dev_lock );
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, NULL );
-  if( !sl ) return FD_ED25519_ERR_ARG;
-  int err = fd_txn_blob_in( sl, blob, blob_sz );
+  fd_ed25519_gpu_slot * sl;
+  int err = fd_slot_take( g, NULL, &sl );
   if( err ) return err;
+  if( (err = fd_txn_blob_in( sl, blob, blob_sz )) ) return fd_slot_settle( g, sl, sl->stream, err );
   if( (err = fd_txn_host_run( g, sl, blob_sz, txn, n_txn, sig_cap, 0UL, kn, 0 )) ) return err;
   fd_txn_pk_off o = fd_txn_pk_layout( g->txn_cap, g->max_sigs );
   uint8_t const * h = g->h_txn_pk;
@@ -2537,18 +2502,6 @@ static int fd_txn_slot_enqueue_( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl,
   return 0;
 }
 
-/* the bounded drain and orphan path of fd_slot_enqueue */
-static int fd_txn_slot_enqueue( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n_txn, void const * blob,
-                                unsigned long blob_sz, fd_ed25519_gpu_txn_t const * txn, hipEvent_t const * ev ) {
-  hipStream_t st = NULL;
-  int err = fd_txn_slot_enqueue_( g, sl, n_txn, blob, blob_sz, txn, &st, ev );
-  if( err && st && fd_wait_query( fd_stream_query, (void *)st, FD_POLL_SPIN_NS, fd_timeout( g ) ) != 1 ) {
-    if( hipEventRecord( sl->done, st ) == hipSuccess ) { sl->ticket = g->next_ticket++; sl->orphan = 1; sl->n_txn = 0UL; }
-    else sl->ticket = ~0UL;
-  }
-  return err;
-}
-
 static int fd_txn_try_submit( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
                               fd_ed25519_gpu_txn_t const * txn, unsigned long * ticket, int timed ) {
   if( !g || !ticket || !txn || !n_txn || n_txn > g->max_sigs || n_txn > FD_TXN_MAX || blob_sz > g->max_blob || (blob_sz && !blob) )
@@ -2583,7 +2536,9 @@ static int fd_txn_try_submit( fd_ed25519_gpu_t * g, unsigned long n_txn, void co
       if( !g->txn_ring_ev[k] && (e = hipEventCreate( &g->txn_ring_ev[k] )) != hipSuccess ) { g->txn_ring_ev[k] = NULL; return fd_gpu_fail( "txn event", e ); }
   fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
   if( !sl ) return 0;                    /* ring full: poll first */
-  err = fd_txn_slot_enqueue( g, sl, n_txn, blob, blob_sz, txn, timed ? g->txn_ring_ev : NULL );
+  hipStream_t st = NULL;
+  err = fd_txn_slot_enqueue_( g, sl, n_txn, blob, blob_sz, txn, &st, timed ? g->txn_ring_ev : NULL );
+  if( err ) err = fd_slot_settle( g, sl, st, err );
   sl->staged = 0;                        /* released, submitted or not, as fd_ed25519_gpu_try_submit2 */
   if( err ) return err;
   sl->ticket = g->next_ticket++;
