@@ -51,6 +51,11 @@ POH_MIXIN = 1        # FD_POH_GPU_MIXIN
 POH_ERR_HASH = -1    # FD_POH_ERR_HASH: the chain does not reach expect
 POH_CHUNK_DEFAULT = 16384
 
+# fd_bmtree_gpu_leaf_t (fd_bmtree_gpu.h): a leaf is blob[off, off+sz)
+BMTREE_LEAF_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4")])
+BMTREE_LEAVES_ARE_NODES = 1   # FD_BMTREE_GPU_LEAVES_ARE_NODES
+BMTREE_LEAF_SZ_MAX = 65535    # FD_BMTREE_GPU_LEAF_SZ_MAX
+
 
 class Stages:
     """what Engine.debug_stages read back from one launch"""
@@ -323,6 +328,37 @@ def lib() -> ctypes.CDLL:
         L.fd_poh_gpu_debug_set_sort.restype = ip
         L.fd_poh_gpu_chunk.argtypes = [vp]
         L.fd_poh_gpu_chunk.restype = ul
+        u = ctypes.c_uint
+        L.fd_poh_gpu_verify_entries_packed.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp, vp, ul, ul]
+        L.fd_poh_gpu_verify_entries_packed.restype = ip
+        L.fd_poh_gpu_verify_entries_dev.argtypes = [vp, ul, vp, ul, vp, vp, vp, vp, ul, vp, vp, ul, ul, vp, vp]
+        L.fd_poh_gpu_verify_entries_dev.restype = ip
+        L.fd_poh_gpu_entries_work_sz.argtypes = [ul, ul]
+        L.fd_poh_gpu_entries_work_sz.restype = ul
+        for w in ("20", "32"):
+            f = getattr(L, f"fd_bmtree{w}_hash_leaf")
+            f.argtypes, f.restype = [vp, vp, ul], vp
+            for name in ("commit_align", "commit_footprint"):
+                f = getattr(L, f"fd_bmtree{w}_{name}")
+                f.argtypes, f.restype = [], ul
+            f = getattr(L, f"fd_bmtree{w}_commit_init")
+            f.argtypes, f.restype = [vp], vp
+            f = getattr(L, f"fd_bmtree{w}_commit_leaf_cnt")
+            f.argtypes, f.restype = [vp], ul
+            f = getattr(L, f"fd_bmtree{w}_commit_append")
+            f.argtypes, f.restype = [vp, vp, ul], vp
+            f = getattr(L, f"fd_bmtree{w}_commit_fini")
+            f.argtypes, f.restype = [vp], vp
+        L.fd_bmtree_roots_batch.argtypes = [u, u, ul, vp, vp, vp, ul, ul, vp, vp, ip]
+        L.fd_bmtree_roots_batch.restype = ip
+        L.fd_bmtree_gpu_roots_packed.argtypes = [vp, u, u, ul, vp, vp, vp, ul, ul, vp, vp]
+        L.fd_bmtree_gpu_roots_packed.restype = ip
+        L.fd_bmtree_gpu_roots_dev.argtypes = [vp, u, u, ul, vp, ul, vp, vp, ul, ul, vp, ul, vp, vp, vp]
+        L.fd_bmtree_gpu_roots_dev.restype = ip
+        L.fd_bmtree_gpu_work_sz.argtypes = [ul, ul]
+        L.fd_bmtree_gpu_work_sz.restype = ul
+        L.fd_bmtree_gpu_merge_passes.argtypes = [u, ul, vp]
+        L.fd_bmtree_gpu_merge_passes.restype = ul
         _lib = L
     return _lib
 
@@ -799,6 +835,62 @@ class Engine:
         if lib().fd_poh_gpu_debug_set_sort(self._h, 1 if on else 0):
             raise EngineError(f"poh_debug_sort: {last_error()}")
 
+    def poh_verify_entries(self, entries: np.ndarray, n_max: int, leaf_cnt: np.ndarray, leaves: np.ndarray, blob: np.ndarray,
+                           leaf_max: int, states: bool = False):
+        """fd_poh_gpu_verify_entries_packed: poh_verify where entry i with
+        leaf_cnt[i] > 0 takes its mixin from the bmtree32 root of its leaves
+        (BMTREE_LEAF_DTYPE descriptors into blob), computed on the device."""
+        entries = np.ascontiguousarray(entries, dtype=POH_ENTRY_DTYPE)
+        leaf_cnt, leaves, blob = _bmtree_inputs(leaf_cnt, leaves, blob)
+        n = len(entries)
+        if len(leaf_cnt) != n:
+            raise ValueError("poh_verify_entries: one leaf count per entry")
+        out = np.empty(n, dtype=np.int32)
+        st = np.empty((n, 32), dtype=np.uint8) if states else None
+        err = lib().fd_poh_gpu_verify_entries_packed(self._h, n, _p(entries), n_max, _p(out), _p(st) if states else None,
+                                                     _p(leaf_cnt), _p(leaves), _p(blob), blob.nbytes, leaf_max)
+        if err:
+            raise EngineError(f"poh_verify_entries: {strerror(err)}: {last_error()}")
+        return (out, st) if states else out
+
+    def poh_verify_entries_dev(self, n: int, d_entries: int, n_max: int, d_out: int, d_states: int, d_work: int, d_first: int,
+                               n_leaves: int, d_leaves: int, d_blob: int, blob_sz: int, leaf_max: int, d_tree_work: int,
+                               stream: int = 0) -> None:
+        """fd_poh_gpu_verify_entries_dev (raw device pointers; d_tree_work:
+        poh_entries_work_sz(n, n_leaves) bytes); queues the launches and
+        returns.  The entries are written (mixin, _pad)."""
+        err = lib().fd_poh_gpu_verify_entries_dev(self._h, n, d_entries, n_max, d_out, d_states or None, d_work or None,
+                                                  d_first or None, n_leaves, d_leaves or None, d_blob or None, blob_sz, leaf_max,
+                                                  d_tree_work or None, stream or None)
+        if err:
+            raise EngineError(f"poh_verify_entries_dev: {strerror(err)}: {last_error()}")
+
+    def bmtree_roots(self, width: int, leaf_cnt: np.ndarray, leaves: np.ndarray, blob: np.ndarray, leaf_max: int, flags: int = 0):
+        """fd_bmtree_gpu_roots_packed: the Merkle root of every tree as an
+        (n_trees, 32) array (width 20: bytes 20..31 zero) and its code (0, or
+        ERR_ARG for a refused tree, whose root is zero)."""
+        leaf_cnt, leaves, blob = _bmtree_inputs(leaf_cnt, leaves, blob)
+        n = len(leaf_cnt)
+        roots = np.empty((n, 32), dtype=np.uint8)
+        codes = np.empty(n, dtype=np.int32)
+        err = lib().fd_bmtree_gpu_roots_packed(self._h, width, flags, n, _p(leaf_cnt), _p(leaves), _p(blob), blob.nbytes, leaf_max,
+                                               _p(roots), _p(codes))
+        if err:
+            raise EngineError(f"bmtree_roots: {strerror(err)}: {last_error()}")
+        return roots, codes
+
+    def bmtree_roots_dev(self, width: int, n_trees: int, d_first: int, n_leaves: int, d_leaves: int, d_blob: int, blob_sz: int,
+                         leaf_max: int, d_roots: int, root_stride: int, d_codes: int, d_work: int, stream: int = 0,
+                         flags: int = 0) -> None:
+        """fd_bmtree_gpu_roots_dev: device-resident (raw device pointers;
+        d_work: bmtree_work_sz(n_trees, n_leaves) bytes); queues the launches
+        and returns."""
+        err = lib().fd_bmtree_gpu_roots_dev(self._h, width, flags, n_trees, d_first or None, n_leaves, d_leaves or None,
+                                            d_blob or None, blob_sz, leaf_max, d_roots or None, root_stride, d_codes or None,
+                                            d_work or None, stream or None)
+        if err:
+            raise EngineError(f"bmtree_roots_dev: {strerror(err)}: {last_error()}")
+
     def sha512(self, msgs, is384: bool = False) -> list:
         """SHA-512 (SHA-384) digests of byte strings on the device."""
         n = len(msgs)
@@ -1102,6 +1194,87 @@ def poh_chain(seed: bytes, hashes: np.ndarray, entries: np.ndarray) -> np.ndarra
 
 def poh_work_sz(n: int) -> int:
     return lib().fd_poh_gpu_work_sz(n)
+
+
+def poh_entries_work_sz(n: int, n_leaves: int) -> int:
+    return lib().fd_poh_gpu_entries_work_sz(n, n_leaves)
+
+
+def _bmtree_inputs(leaf_cnt, leaves, blob):
+    leaf_cnt = np.ascontiguousarray(leaf_cnt, dtype=np.uint32)
+    leaves = np.ascontiguousarray(leaves, dtype=BMTREE_LEAF_DTYPE)
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    if int(leaf_cnt.sum(dtype=np.uint64)) != len(leaves):
+        raise ValueError("bmtree: the leaf counts do not sum to the number of descriptors")
+    return leaf_cnt, leaves, blob
+
+
+def _bmtree_node_buf(count: int):
+    """count 32-byte nodes in a 32-aligned buffer: (keepalive, address)"""
+    raw = np.zeros(32 * count + 32, dtype=np.uint8)
+    a = (raw.ctypes.data + 31) & ~31
+    return raw, a
+
+
+def bmtree_hash_leaf(width: int, data: bytes) -> bytes:
+    """fd_bmtree{20,32}_hash_leaf on the host: the first `width` bytes of SHA-256( 0x00 || data )"""
+    raw, a = _bmtree_node_buf(1)
+    data = bytes(data)
+    getattr(lib(), f"fd_bmtree{width}_hash_leaf")(a, data, len(data))
+    return ctypes.string_at(a, width)
+
+
+class BmtreeCommit:
+    """fd_bmtree{20,32}_commit_*: an incremental Merkle commitment on the host"""
+
+    def __init__(self, width: int):
+        if width not in (20, 32):
+            raise ValueError("bmtree: width 20 or 32")
+        self.width, L = width, lib()
+        self._f = {k: getattr(L, f"fd_bmtree{width}_commit_{k}") for k in ("align", "footprint", "init", "leaf_cnt", "append", "fini")}
+        al, fp = self._f["align"](), self._f["footprint"]()
+        self._raw = np.zeros(fp + al, dtype=np.uint8)
+        self._mem = (self._raw.ctypes.data + al - 1) & ~(al - 1)
+        if self._f["init"](self._mem) != self._mem:
+            raise EngineError("bmtree commit_init")
+
+    @property
+    def leaf_cnt(self) -> int:
+        return self._f["leaf_cnt"](self._mem)
+
+    def append(self, nodes) -> "BmtreeCommit":
+        """nodes: byte strings of `width` (or 32) bytes each, in order"""
+        raw, a = _bmtree_node_buf(len(nodes))
+        for i, nd in enumerate(nodes):
+            ctypes.memmove(a + 32 * i, bytes(nd), len(nd))
+        self._f["append"](self._mem, a, len(nodes))
+        return self
+
+    def fini(self) -> bytes:
+        return ctypes.string_at(self._f["fini"](self._mem), self.width)
+
+
+def bmtree_roots_batch(width: int, leaf_cnt, leaves, blob, leaf_max: int, flags: int = 0, nthreads: int = 8):
+    """fd_bmtree_roots_batch: Engine.bmtree_roots's semantics on host threads"""
+    leaf_cnt, leaves, blob = _bmtree_inputs(leaf_cnt, leaves, blob)
+    n = len(leaf_cnt)
+    roots = np.empty((n, 32), dtype=np.uint8)
+    codes = np.empty(n, dtype=np.int32)
+    err = lib().fd_bmtree_roots_batch(width, flags, n, _p(leaf_cnt), _p(leaves), _p(blob), blob.nbytes, leaf_max, _p(roots), _p(codes),
+                                      nthreads)
+    if err:
+        raise EngineError(f"bmtree_roots_batch: {strerror(err)}")
+    return roots, codes
+
+
+def bmtree_work_sz(n_trees: int, n_leaves: int) -> int:
+    return lib().fd_bmtree_gpu_work_sz(n_trees, n_leaves)
+
+
+def bmtree_merge_passes(width: int, leaf_cnt) -> int:
+    """64-lane compression passes the merge launches issue for these tree sizes"""
+    leaf_cnt = np.ascontiguousarray(leaf_cnt, dtype=np.uint32)
+    return lib().fd_bmtree_gpu_merge_passes(width, len(leaf_cnt), _p(leaf_cnt))
 
 
 def txn_claims(blob: np.ndarray, txns: np.ndarray):

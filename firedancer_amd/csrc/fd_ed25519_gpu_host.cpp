@@ -32,6 +32,7 @@
 #include "fd_ed25519_gpu_txn_claim.h"
 #include "fd_sha512_gpu_private.h"
 #include "fd_poh_gpu_private.h"
+#include "fd_bmtree_gpu_private.h"
 
 #define FD_GPU_DEPTH_DEFAULT 3
 #define FD_GPU_DEPTH_MAX     8
@@ -242,17 +243,19 @@ struct fd_ed25519_gpu {
   unsigned long txn_ring_allocs;  /* slots whose transaction scratch was allocated (fd_ed25519_gpu_txn_ring_allocs) */
   hipEvent_t    txn_ring_ev[4];   /* fd_ed25519_gpu_txn_ring_timed: around the front kernel and the reduce */
   fd_poh_gpu_ext_t poh;           /* Proof-of-History chains: fd_poh_gpu.cpp's own stream and scratch, made on first use */
+  fd_bmtree_gpu_ext_t bmtree;     /* Merkle trees: fd_bmtree_gpu.cpp's own stream and scratch, likewise */
   fd_ring_lock  lock;
 };
 
 extern "C" fd_poh_gpu_ext_t * fd_ed25519_gpu_poh_ext( fd_ed25519_gpu_t * g ) { return &g->poh; }
+extern "C" fd_bmtree_gpu_ext_t * fd_ed25519_gpu_bmtree_ext( fd_ed25519_gpu_t * g ) { return &g->bmtree; }
 
 static inline long fd_timeout( fd_ed25519_gpu_t const * g ) { return __atomic_load_n( &g->timeout_ns, __ATOMIC_RELAXED ); }
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if( e_ != hipSuccess ) { fd_gpu_fail( #call, e_ ); goto fail; } } while(0)
 
 extern "C" char const * fd_ed25519_gpu_last_error( void ) { return fd_gpu_err; }
-/* for the host units outside this file (fd_poh_gpu.cpp) */
+/* for the host units outside this file (fd_poh_gpu.cpp, fd_bmtree_gpu.cpp) */
 extern "C" void fd_ed25519_gpu_set_error( char const * what ) { snprintf( fd_gpu_err, sizeof(fd_gpu_err), "%s", what ); }
 
 extern "C" int fd_ed25519_gpu_device_cnt( void ) {
@@ -479,6 +482,7 @@ extern "C" void fd_ed25519_gpu_delete( fd_ed25519_gpu_t * g ) {
     }
   }
   if( g->poh.fini ) g->poh.fini( g->poh.ctx );
+  if( g->bmtree.fini ) g->bmtree.fini( g->bmtree.ctx );
   for( int k=0; k<FD_REG_MAX; k++ ) if( g->reg[k].p ) fd_reg_release( (void *)g->reg[k].p );
   for( int s=0; s<g->depth; s++ ) {
     fd_ed25519_gpu_slot * sl = &g->slot[s];

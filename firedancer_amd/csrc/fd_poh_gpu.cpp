@@ -9,7 +9,13 @@
    The packed call orders the lanes by n descending.  Each wave then holds
    chains of about one length, the long chains start in the first launch,
    and launch j is given only the prefix of lanes with n > j C: the lanes
-   past it are done and would cost a load each. */
+   past it are done and would cost a load each.
+
+   The entries calls take an entry's leaves instead of its mixin: ahead of
+   the first fd_k_poh launch, on the same stream, the tree launcher
+   (fd_bmtree_gpu_private.h) writes each entry's bmtree32 root into the
+   mixin field of its device copy, and a gate kernel marks the entries
+   whose leaves cannot be used so that fd_k_poh refuses them unhashed. */
 
 #include <stdio.h>
 #include <string.h>
@@ -19,6 +25,7 @@
 #include <mutex>
 #include <vector>
 #include "fd_poh_gpu_private.h"
+#include "fd_bmtree_gpu_private.h"
 
 #define FD_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -40,6 +47,17 @@ struct fd_poh_ctx {
   unsigned long chunk;       /* hashes per lane per launch */
   int           nosort;      /* experiments (fd_poh_gpu_debug_set_sort): the packed call keeps the caller's lane order */
   int           busy;        /* a call gave up waiting: `done` has not been seen complete since */
+  unsigned long t_cap, t_in_cap;   /* the entries call's trees: bytes of d_tree and h_tree */
+  uint8_t *     d_tree;      /* first | leaves | blob | tree codes | tree work */
+  uint8_t *     h_tree;      /* pinned: first | leaves | blob */
+};
+
+/* the leaves of fd_poh_gpu_verify_entries_packed */
+struct fd_poh_trees {
+  uint32_t const *             leaf_cnt;
+  fd_bmtree_gpu_leaf_t const * leaves;
+  void const *                 blob;
+  unsigned long                blob_sz, leaf_max, n_leaves;
 };
 
 static int fd_poh_fail( char const * what, hipError_t e ) {
@@ -78,7 +96,31 @@ static void fd_poh_free_scratch( fd_poh_ctx * c ) {
   if( c->d_buf ) hipFree( c->d_buf );
   if( c->h_in  ) hipHostFree( c->h_in );
   if( c->h_out ) hipHostFree( c->h_out );
-  c->d_buf = c->h_in = c->h_out = NULL; c->cap = 0UL;
+  if( c->d_tree ) hipFree( c->d_tree );
+  if( c->h_tree ) hipHostFree( c->h_tree );
+  c->d_buf = c->h_in = c->h_out = c->d_tree = c->h_tree = NULL; c->cap = c->t_cap = c->t_in_cap = 0UL;
+}
+
+static inline unsigned long fd_poh_r16( unsigned long n ) { return ( n + 15UL ) & ~15UL; }
+
+static int fd_poh_ensure_trees( fd_poh_ctx * c, unsigned long d_sz, unsigned long in_sz ) {
+  hipError_t e = hipSuccess;
+  if( d_sz > c->t_cap ) {
+    if( c->d_tree ) hipFree( c->d_tree );
+    c->d_tree = NULL; c->t_cap = 0UL;
+    unsigned long cap = fd_poh_r16( d_sz + d_sz/8UL );
+    e = hipMalloc( (void **)&c->d_tree, cap );
+    if( e == hipSuccess ) c->t_cap = cap;
+  }
+  if( e == hipSuccess && in_sz > c->t_in_cap ) {
+    if( c->h_tree ) hipHostFree( c->h_tree );
+    c->h_tree = NULL; c->t_in_cap = 0UL;
+    unsigned long cap = fd_poh_r16( in_sz + in_sz/8UL );
+    e = hipHostMalloc( (void **)&c->h_tree, cap, hipHostMallocDefault );
+    if( e == hipSuccess ) c->t_in_cap = cap;
+  }
+  if( e != hipSuccess ) return fd_poh_fail( "poh tree scratch", e );
+  return 0;
 }
 
 /* fd_ed25519_gpu_delete: the engine's own streams have drained.  If ours
@@ -169,8 +211,9 @@ FD_EXPORT unsigned long fd_poh_gpu_chunk( fd_ed25519_gpu_t * gpu ) {
   return c->chunk;
 }
 
-FD_EXPORT int fd_poh_gpu_verify_packed( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t const * entries,
-                                        unsigned long n_max, int * out, void * state_out_opt ) {
+/* tr NULL: fd_poh_gpu_verify_packed; else the entries call, its arguments checked */
+static int fd_poh_packed( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t const * entries,
+                          unsigned long n_max, int * out, void * state_out_opt, fd_poh_trees const * tr ) {
   if( n > FD_POH_N_MAX || ( n && ( !entries || !out ) ) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
   if( !gpu ) gpu = fd_ed25519_gpu_default();
@@ -184,7 +227,10 @@ FD_EXPORT int fd_poh_gpu_verify_packed( fd_ed25519_gpu_t * gpu, unsigned long n,
      refused entries count as n = 0 (the first launch writes their code).
      Chains below 2^32 hashes sort as one 64-bit key each. */
   unsigned long max_n = 0UL;
-  for( unsigned long i=0; i<n; i++ ) if( fd_poh_entry_ok( entries + i, n_max ) && entries[i].n > max_n ) max_n = entries[i].n;
+  auto ok = [&]( unsigned long i ) {    /* what is known here of what the first launch will refuse */
+    return fd_poh_entry_ok( entries + i, n_max ) && !( tr && tr->leaf_cnt[i] && !( entries[i].flags & FD_POH_GPU_MIXIN ) );
+  };
+  for( unsigned long i=0; i<n; i++ ) if( ok( i ) && entries[i].n > max_n ) max_n = entries[i].n;
   unsigned long launches = fd_poh_launches( max_n, C );
   if( launches > FD_POH_GPU_LAUNCH_MAX ) return FD_ED25519_ERR_ARG;
   std::vector<uint32_t> order( n );
@@ -194,12 +240,12 @@ FD_EXPORT int fd_poh_gpu_verify_packed( fd_ed25519_gpu_t * gpu, unsigned long n,
   } else if( max_n <= 0xffffffffUL ) {
     std::vector<uint64_t> key( n );
     for( unsigned long i=0; i<n; i++ )
-      key[i] = ( ( fd_poh_entry_ok( entries + i, n_max ) ? entries[i].n : 0UL ) << 32 ) | ( 0xffffffffUL - i );
+      key[i] = ( ( ok( i ) ? entries[i].n : 0UL ) << 32 ) | ( 0xffffffffUL - i );
     std::sort( key.begin(), key.end(), std::greater<uint64_t>() );
     for( unsigned long i=0; i<n; i++ ) { order[i] = (uint32_t)( 0xffffffffUL - ( key[i] & 0xffffffffUL ) ); len[i] = key[i] >> 32; }
   } else {
     for( unsigned long i=0; i<n; i++ ) order[i] = (uint32_t)i;
-    auto eff = [&]( uint32_t i ) { return fd_poh_entry_ok( entries + i, n_max ) ? entries[i].n : 0UL; };
+    auto eff = [&]( uint32_t i ) { return ok( i ) ? entries[i].n : 0UL; };
     std::stable_sort( order.begin(), order.end(), [&]( uint32_t a, uint32_t b ) { return eff( a ) > eff( b ); } );
     for( unsigned long i=0; i<n; i++ ) len[i] = eff( order[i] );
   }
@@ -224,7 +270,33 @@ FD_EXPORT int fd_poh_gpu_verify_packed( fd_ed25519_gpu_t * gpu, unsigned long n,
   memcpy( c->h_in, entries, n * FD_POH_ENT_SZ );
   memcpy( c->h_in + n4 * FD_POH_ENT_SZ, order.data(), n * 4UL );
 
+  /* the trees' inputs, staged like the entries */
+  unsigned long first_sz = 0UL, leaf_sz = 0UL, t_in_sz = 0UL, tcode_sz = 0UL;
+  if( tr && tr->n_leaves ) {
+    first_sz = fd_poh_r16( 4UL*( n + 1UL ) ); leaf_sz = fd_poh_r16( 8UL*tr->n_leaves ); tcode_sz = fd_poh_r16( 4UL*n );
+    t_in_sz  = first_sz + leaf_sz + fd_poh_r16( tr->blob_sz );
+    err = fd_poh_ensure_trees( c, t_in_sz + tcode_sz + fd_bmtree_gpu_work_sz( n, tr->n_leaves ), t_in_sz );
+    if( err ) return err;
+    uint32_t * h_first = (uint32_t *)c->h_tree;
+    unsigned long run = 0UL;
+    for( unsigned long i=0; i<n; i++ ) { h_first[i] = (uint32_t)run; run += tr->leaf_cnt[i]; }
+    h_first[n] = (uint32_t)run;
+    memcpy( c->h_tree + first_sz, tr->leaves, 8UL*tr->n_leaves );
+    if( tr->blob_sz ) memcpy( c->h_tree + first_sz + leaf_sz, tr->blob, tr->blob_sz );
+  }
+
   e = hipMemcpyAsync( d_ent, c->h_in, in_sz, hipMemcpyHostToDevice, c->stream );
+  if( e == hipSuccess && t_in_sz ) e = hipMemcpyAsync( c->d_tree, c->h_tree, t_in_sz, hipMemcpyHostToDevice, c->stream );
+  if( e == hipSuccess && t_in_sz ) {    /* roots into the mixins, then the gate, ahead of the first chain launch */
+    uint8_t * d_tcodes = c->d_tree + t_in_sz;
+    int r = fd_bmtree_gpu_roots_dev_flags( gpu, 32U, FD_BMTREE_GPU_SKIP_EMPTY, n, (uint32_t const *)c->d_tree, tr->n_leaves,
+                                           (fd_bmtree_gpu_leaf_t const *)( c->d_tree + first_sz ), c->d_tree + first_sz + leaf_sz,
+                                           tr->blob_sz, tr->leaf_max, d_ent + 32UL, FD_POH_ENT_SZ, (int *)d_tcodes, d_tcodes + tcode_sz,
+                                           c->stream );
+    if( r ) e = hipErrorLaunchFailure;
+    else    e = fd_bmtree_gpu_poh_gate_launch( (uint32_t)n, (uint32_t const *)c->d_tree, (int32_t const *)d_tcodes,
+                                               (fd_poh_gpu_entry_t *)d_ent, c->stream );
+  }
   unsigned long lanes = n;
   for( unsigned long j=0; j<launches && e == hipSuccess; j++ ) {
     if( j ) {                           /* the lanes with more than j C hashes */
@@ -244,6 +316,57 @@ FD_EXPORT int fd_poh_gpu_verify_packed( fd_ed25519_gpu_t * gpu, unsigned long n,
   memcpy( out, c->h_out, n * 4UL );
   if( state_out_opt ) memcpy( state_out_opt, c->h_out + n4 * 4UL, n * 32UL );
   return 0;
+}
+
+FD_EXPORT int fd_poh_gpu_verify_packed( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t const * entries,
+                                        unsigned long n_max, int * out, void * state_out_opt ) {
+  return fd_poh_packed( gpu, n, entries, n_max, out, state_out_opt, NULL );
+}
+
+FD_EXPORT int fd_poh_gpu_verify_entries_packed( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t const * entries,
+                                                unsigned long n_max, int * out, void * state_out_opt, uint32_t const * leaf_cnt,
+                                                fd_bmtree_gpu_leaf_t const * leaves, void const * blob, unsigned long blob_sz,
+                                                unsigned long leaf_max ) {
+  if( n > FD_POH_N_MAX || ( n && ( !entries || !out || !leaf_cnt ) ) ) return FD_ED25519_ERR_ARG;
+  if( blob_sz > 0xffffffffUL || !leaf_max ) return FD_ED25519_ERR_ARG;
+  fd_poh_trees tr = { leaf_cnt, leaves, blob, blob_sz, leaf_max, 0UL };
+  for( unsigned long i=0; i<n; i++ ) tr.n_leaves += leaf_cnt[i];
+  if( tr.n_leaves > FD_BMTREE_GPU_LEAVES_MAX || ( tr.n_leaves && !leaves ) || ( blob_sz && !blob ) ) return FD_ED25519_ERR_ARG;
+  return fd_poh_packed( gpu, n, entries, n_max, out, state_out_opt, &tr );
+}
+
+FD_EXPORT unsigned long fd_poh_gpu_entries_work_sz( unsigned long n, unsigned long n_leaves ) {
+  unsigned long w = fd_bmtree_gpu_work_sz( n, n_leaves );
+  return w ? fd_poh_r16( 4UL*( n ? n : 1UL ) ) + w : 0UL;
+}
+
+FD_EXPORT int fd_poh_gpu_verify_entries_dev( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t * d_entries, unsigned long n_max,
+                                             int * d_out, void * d_state_out_opt, void * d_work, uint32_t const * d_first,
+                                             unsigned long n_leaves, fd_bmtree_gpu_leaf_t const * d_leaves, void const * d_blob,
+                                             unsigned long blob_sz, unsigned long leaf_max, void * d_tree_work, void * stream ) {
+  if( n > FD_POH_N_MAX || ( n && ( !d_entries || !d_out || !d_work || !d_first || !d_tree_work ) ) ) return FD_ED25519_ERR_ARG;
+  if( ( (uintptr_t)d_work | (uintptr_t)d_state_out_opt | (uintptr_t)d_tree_work ) & 15UL ) return FD_ED25519_ERR_ARG;
+  if( ( (uintptr_t)d_entries & 7UL ) || blob_sz > 0xffffffffUL || !leaf_max || n_leaves > FD_BMTREE_GPU_LEAVES_MAX ) return FD_ED25519_ERR_ARG;
+  if( n_leaves && ( !d_leaves || ( blob_sz && !d_blob ) ) ) return FD_ED25519_ERR_ARG;
+  if( !n ) return 0;
+  if( !gpu ) gpu = fd_ed25519_gpu_default();
+  if( !gpu ) return FD_ED25519_ERR_GPU;
+  fd_poh_ctx * c = fd_poh_ctx_get( gpu );
+  if( !c ) return FD_ED25519_ERR_GPU;
+  { std::lock_guard<std::mutex> guard( c->lock );
+    if( fd_poh_launches( n_max, c->chunk ) > FD_POH_GPU_LAUNCH_MAX ) return FD_ED25519_ERR_ARG; }   /* before anything is queued */
+  hipError_t e = hipSetDevice( c->device );
+  if( e != hipSuccess ) return fd_poh_fail( "hipSetDevice", e );
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if( n_leaves ) {
+    uint8_t * d_tcodes = (uint8_t *)d_tree_work;
+    int r = fd_bmtree_gpu_roots_dev_flags( gpu, 32U, FD_BMTREE_GPU_SKIP_EMPTY, n, d_first, n_leaves, d_leaves, d_blob, blob_sz, leaf_max,
+                                           (uint8_t *)d_entries + 32UL, FD_POH_ENT_SZ, (int *)d_tcodes, d_tcodes + fd_poh_r16( 4UL*n ), st );
+    if( r ) return r;
+    e = fd_bmtree_gpu_poh_gate_launch( (uint32_t)n, d_first, (int32_t const *)d_tcodes, d_entries, st );
+    if( e != hipSuccess ) return fd_poh_fail( "poh gate launch", e );
+  }
+  return fd_poh_gpu_verify_dev( gpu, n, d_entries, n_max, d_out, d_state_out_opt, d_work, st );
 }
 
 FD_EXPORT int fd_poh_gpu_verify_dev( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t const * d_entries, unsigned long n_max,

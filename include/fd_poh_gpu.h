@@ -27,6 +27,7 @@
    fd_poh_verify_batch). */
 
 #include "fd_ed25519_gpu.h"
+#include "fd_bmtree_gpu.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -114,6 +115,61 @@ fd_poh_gpu_verify_dev( fd_ed25519_gpu_t *         gpu,
                        void *                     stream );
 
 unsigned long fd_poh_gpu_work_sz( unsigned long n );
+
+/* Entries from leaves.  fd_poh_gpu_verify_packed with, per entry, the
+   leaves of its mixin instead of the mixin: entry i has leaf_cnt[i] leaves
+   (fd_bmtree_gpu.h: descriptors into blob, entry 0's first; typically the
+   64-byte signatures of its transactions, in place in their payloads).
+
+   An entry with leaf_cnt[i] == 0 is handled exactly as by
+   fd_poh_gpu_verify_packed.  An entry with leaves must carry
+   FD_POH_GPU_MIXIN; its mixin field is not read: the mixin is the bmtree32
+   root of its leaves, computed on the device ahead of the chains.  Such an
+   entry gets FD_ED25519_ERR_ARG and is never hashed if it lacks the flag or
+   its tree is refused (leaf_cnt[i] > leaf_max, a leaf out of the blob or
+   above FD_BMTREE_GPU_LEAF_SZ_MAX).  Returns as fd_poh_gpu_verify_packed;
+   FD_ED25519_ERR_ARG also for a NULL leaf_cnt, leaf_max == 0,
+   blob_sz >= 2^32 or more than FD_BMTREE_GPU_LEAVES_MAX leaves. */
+int
+fd_poh_gpu_verify_entries_packed( fd_ed25519_gpu_t *           gpu,
+                                  unsigned long                n,
+                                  fd_poh_gpu_entry_t const *   entries,
+                                  unsigned long                n_max,
+                                  int *                        out,
+                                  void *                       state_out_opt,
+                                  uint32_t const *             leaf_cnt,
+                                  fd_bmtree_gpu_leaf_t const * leaves,
+                                  void const *                 blob,
+                                  unsigned long                blob_sz,
+                                  unsigned long                leaf_max );
+
+/* Device-resident: fd_poh_gpu_verify_dev's arguments, then the trees' as in
+   fd_bmtree_gpu_roots_dev (d_first: the n + 1 exclusive prefix of the leaf
+   counts) and d_tree_work (fd_poh_gpu_entries_work_sz( n, n_leaves ) bytes,
+   16-byte aligned).  d_entries is written: the root goes into the mixin
+   field of an entry with leaves (root_stride 112, offset 32), and _pad
+   becomes nonzero where such an entry is refused, which is how the chain
+   kernel comes to refuse it.  The tree launches (their number from
+   min( leaf_max, n_leaves ) alone) are queued on `stream` ahead of the
+   chain launches; no host synchronisation. */
+int
+fd_poh_gpu_verify_entries_dev( fd_ed25519_gpu_t *           gpu,
+                               unsigned long                n,
+                               fd_poh_gpu_entry_t *         d_entries,
+                               unsigned long                n_max,
+                               int *                        d_out,
+                               void *                       d_state_out_opt,
+                               void *                       d_work,
+                               uint32_t const *             d_first,
+                               unsigned long                n_leaves,
+                               fd_bmtree_gpu_leaf_t const * d_leaves,
+                               void const *                 d_blob,
+                               unsigned long                blob_sz,
+                               unsigned long                leaf_max,
+                               void *                       d_tree_work,
+                               void *                       stream );
+
+unsigned long fd_poh_gpu_entries_work_sz( unsigned long n, unsigned long n_leaves );
 
 /* Pure host code: start and expect of a run of n consecutive entries from
    the hash before the run and the hashes the entries claim: start[0] =

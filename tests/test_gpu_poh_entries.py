@@ -1,0 +1,169 @@
+"""Proof-of-History entries from leaves on the device
+(Engine.poh_verify_entries and Engine.poh_verify_entries_dev): an entry with
+leaves takes its mixin from the bmtree32 root of its leaves.  Codes and final
+states must equal Engine.poh_verify on the same entries carrying the model's
+roots (tests/bmtree_grid.py) as mixins, and hashlib's."""
+import functools
+
+import numpy as np
+import pytest
+
+import bmtree_grid as bg
+import firedancer_amd as fa
+import poh_grid as pg
+
+pytestmark = pytest.mark.gpu
+
+CHUNKS = [1, 4, 64]
+COUNT = 130
+
+
+@pytest.fixture
+def chunk(engine):
+    def set_(C):
+        engine.poh_chunk = C
+    yield set_
+    engine.poh_chunk = 0
+
+
+@functools.lru_cache(maxsize=None)
+def _batch(C):
+    """130 entries cycling ticks, caller-mixin entries and leaf entries with
+    0..9 leaves over poh_grid's lengths; every 7th expect has one bit wrong.
+    Returns (entries for the entries call, the same with the model's roots
+    as mixins, leaf_cnt, leaves, blob, codes, states)."""
+    rng = np.random.default_rng(500 + C)
+    lengths = pg.grid_lengths(C)
+    trees, kinds = [], []
+    for i in range(COUNT):
+        kind = i % 3                                   # 0 tick, 1 caller's mixin, 2 leaves
+        n_leaf = (i // 3) % 10 if kind == 2 else 0
+        if kind == 2 and n_leaf == 0:
+            kind = 1                                   # a leaf entry without leaves is a caller-mixin entry
+        kinds.append(kind)
+        trees.append([rng.bytes(64) for _ in range(n_leaf)])
+    cnt, leaves, blob = bg.pack(trees, align_of=lambda k: 5 * k)   # signatures at any alignment, as inside payloads
+    ent = np.zeros(COUNT, fa.POH_ENTRY_DTYPE)
+    ref = np.zeros(COUNT, fa.POH_ENTRY_DTYPE)
+    codes = np.zeros(COUNT, np.int32)
+    states = np.zeros((COUNT, 32), np.uint8)
+    for i in range(COUNT):
+        n = lengths[(i * 5 + i // 9) % len(lengths)]
+        start = rng.bytes(32)
+        mixin = None if kinds[i] == 0 else rng.bytes(32) if kinds[i] == 1 else bg.root(trees[i], 32)
+        pg.entry(ref[i], start, n, mixin)
+        states[i] = ref[i]["expect"]
+        if i % 7 == 3:
+            ref[i]["expect"][int(rng.integers(32))] ^= 1 << int(rng.integers(8))
+            codes[i] = fa.POH_ERR_HASH
+        ent[i] = ref[i]
+        if kinds[i] != 1:
+            ent[i]["mixin"] = np.frombuffer(rng.bytes(32), np.uint8)   # garbage: unread (tick) or overwritten (leaves)
+    assert set(cnt.tolist()) == set(range(10))
+    return ent, ref, cnt, leaves, blob, codes, states
+
+
+@pytest.mark.parametrize("C", CHUNKS)
+def test_entries_packed(engine, chunk, C):
+    ent, ref, cnt, leaves, blob, codes, states = _batch(C)
+    chunk(C)
+    want_c, want_s = engine.poh_verify(ref, 2 * C + 1, states=True)
+    assert (want_c == codes).all() and (want_s == states).all()
+    before = ent.copy()
+    got_c, got_s = engine.poh_verify_entries(ent, 2 * C + 1, cnt, leaves, blob, 9, states=True)
+    assert (got_c == want_c).all()
+    assert (got_s == want_s).all()
+    assert (ent == before).all()                       # the caller's entries are not written
+    assert (engine.poh_verify_entries(ent, 2 * C + 1, cnt, leaves, blob, 9) == want_c).all()
+    # no leaves at all: exactly poh_verify
+    zero = np.zeros(COUNT, np.uint32)
+    none = np.zeros(0, fa.BMTREE_LEAF_DTYPE)
+    a, b = engine.poh_verify_entries(ref, 2 * C + 1, zero, none, blob, 9, states=True)
+    assert (a == want_c).all() and (b == want_s).all()
+
+
+@pytest.mark.parametrize("C", CHUNKS)
+@pytest.mark.parametrize("own_stream", [False, True])
+def test_entries_dev(engine, chunk, C, own_stream):
+    import torch
+    ent, ref, cnt, leaves, blob, codes, states = _batch(C)
+    chunk(C)
+    dev = torch.device("cuda", 0)
+    N = len(leaves)
+    first = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32)
+    d_ent = torch.from_numpy(ent.view(np.uint8).copy()).to(dev)
+    d_first = torch.from_numpy(first.view(np.int32).copy()).to(dev)
+    d_leaves = torch.from_numpy(leaves.view(np.uint8).copy()).to(dev)
+    d_blob = torch.from_numpy(blob.copy()).to(dev)
+    d_out = torch.full((COUNT,), 77, dtype=torch.int32, device=dev)
+    d_st = torch.full((COUNT, 32), 0x55, dtype=torch.uint8, device=dev)
+    d_work = torch.zeros(fa.poh_work_sz(COUNT), dtype=torch.uint8, device=dev)
+    d_twork = torch.zeros(fa.poh_entries_work_sz(COUNT, N), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    args = (COUNT, d_ent.data_ptr(), 2 * C + 1, d_out.data_ptr(), d_st.data_ptr(), d_work.data_ptr(), d_first.data_ptr(), N,
+            d_leaves.data_ptr(), d_blob.data_ptr(), blob.nbytes, 9, d_twork.data_ptr())
+    if own_stream:
+        stream = torch.cuda.Stream(dev)
+        engine.poh_verify_entries_dev(*args, stream.cuda_stream)
+        stream.synchronize()
+    else:
+        engine.poh_verify_entries_dev(*args)
+        torch.cuda.synchronize()
+    assert (d_out.cpu().numpy() == codes).all()
+    assert (d_st.cpu().numpy() == states).all()
+    # the device copy: roots in the mixins of the leaf entries, everything else as it was
+    after = d_ent.cpu().numpy().view(fa.POH_ENTRY_DTYPE)
+    has = cnt > 0
+    assert (after["mixin"][has] == ref["mixin"][has]).all()
+    assert (after["mixin"][~has] == ent["mixin"][~has]).all()
+    for f in ("start", "expect", "n", "flags", "_pad"):
+        assert (after[f] == ent[f]).all(), f
+
+
+def _small(rng, n_leaf_list):
+    trees = [[rng.bytes(64) for _ in range(k)] for k in n_leaf_list]
+    cnt, leaves, blob = bg.pack(trees)
+    ent = np.zeros(len(trees), fa.POH_ENTRY_DTYPE)
+    for i, t in enumerate(trees):
+        pg.entry(ent[i], rng.bytes(32), 3 + i % 4, bg.root(t, 32) if t else (rng.bytes(32) if i & 1 else None))
+    return trees, cnt, leaves, blob, ent
+
+
+def test_one_signature_bit_wrong(engine, chunk):
+    chunk(4)
+    rng = np.random.default_rng(21)
+    trees, cnt, leaves, blob, ent = _small(rng, [(i * 3) % 7 for i in range(70)])
+    true = ent["expect"].copy()
+    assert (engine.poh_verify_entries(ent, 6, cnt, leaves, blob, 6) == 0).all()
+    first = np.concatenate([[0], np.cumsum(cnt)]).astype(int)
+    victim = 44
+    assert cnt[victim] > 1
+    bad = blob.copy()
+    bad[int(leaves[first[victim] + 1]["off"]) + 17] ^= 0x10
+    got, st = engine.poh_verify_entries(ent, 6, cnt, leaves, bad, 6, states=True)
+    exp = np.zeros(70, np.int32)
+    exp[victim] = fa.POH_ERR_HASH
+    assert (got == exp).all()
+    ok = np.arange(70) != victim
+    assert (st[ok] == true[ok]).all() and (st[victim] != true[victim]).any()
+
+
+def test_leaves_without_flag_refused_trees_and_n_max(engine, chunk):
+    chunk(4)
+    rng = np.random.default_rng(22)
+    trees, cnt, leaves, blob, ent = _small(rng, [(i * 5) % 9 for i in range(67)])
+    true = ent["expect"].copy()
+    exp = np.zeros(67, np.int32)
+    first = np.concatenate([[0], np.cumsum(cnt)]).astype(int)
+    leaves = leaves.copy()
+    over = np.nonzero(cnt == 8)[0].tolist()            # 8 leaves > leaf_max 7
+    assert 0 < cnt[5] < 8 and 0 < cnt[23] < 8 and 0 < cnt[31] < 8 and cnt[9] == 0 and len(over) == 7
+    ent[5]["flags"] = 0                                # leaves without FD_POH_GPU_MIXIN
+    leaves[first[23]]["off"] = len(blob) - 10          # a leaf past the blob: its tree is refused
+    ent[31]["n"] = 7                                   # > n_max, as in poh_verify
+    ent[9]["flags"] |= 2                               # an unknown flag on an entry without leaves
+    for i in [5, 23, 31, 9] + over:
+        exp[i], true[i] = fa.ERR_ARG, 0
+    got, st = engine.poh_verify_entries(ent, 6, cnt, leaves, blob, 7, states=True)
+    assert (got == exp).all()                          # the neighbours are unaffected
+    assert (st == true).all()
