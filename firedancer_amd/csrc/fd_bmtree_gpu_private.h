@@ -2,8 +2,8 @@
 #define HEADER_fd_bmtree_gpu_private_h
 
 /* fd_bmtree_gpu_private.h -- between fd_bmtree_gpu.cpp (host side), the
-   kernel unit fd_bmtree_gpu_kernels.hip, fd_poh_gpu.cpp (entries from
-   leaves) and the engine (fd_ed25519_gpu_host.cpp). */
+   kernel unit fd_bmtree_gpu_kernels.hip and fd_poh_gpu.cpp (entries from
+   leaves). */
 
 #include <hip/hip_runtime.h>
 #include "fd_bmtree_gpu.h"
@@ -90,12 +90,12 @@ extern "C" int fd_bmtree_gpu_roots_dev_flags( fd_ed25519_gpu_t * gpu, unsigned w
                                               void const * d_blob, unsigned long blob_sz, unsigned long leaf_max, void * d_roots,
                                               unsigned long root_stride, int * d_codes, void * d_work, void * stream );
 
-/* The engine's slot for the tree host side: created on first use by
-   fd_bmtree_gpu.cpp; fd_ed25519_gpu_delete calls fini( ctx ) once its own
-   streams have drained. */
-typedef struct { void * ctx; void (*fini)( void * ctx ); } fd_bmtree_gpu_ext_t;
-extern "C" fd_bmtree_gpu_ext_t * fd_ed25519_gpu_bmtree_ext( fd_ed25519_gpu_t * gpu );
-/* what fd_ed25519_gpu_last_error returns on this thread */
-extern "C" void fd_ed25519_gpu_set_error( char const * what );
+/* A packed tree batch as the device reads it: first[0..n] (the running sum
+   of leaf_cnt) | leaves | blob, each part rounded up to 16 bytes.  Returns
+   the parts' sizes and, unless h is NULL, writes the batch to h. */
+typedef struct { unsigned long first_sz, leaf_sz, blob_sz; } fd_bmtree_staged_t;
+extern "C" __attribute__((visibility("hidden")))
+fd_bmtree_staged_t fd_bmtree_gpu_stage( uint8_t * h, unsigned long n, uint32_t const * leaf_cnt, unsigned long n_leaves,
+                                        fd_bmtree_gpu_leaf_t const * leaves, void const * blob, unsigned long blob_sz );
 
 #endif /* HEADER_fd_bmtree_gpu_private_h */

@@ -31,8 +31,7 @@
 #include "fd_ed25519_gpu_txn_private.h"
 #include "fd_ed25519_gpu_txn_claim.h"
 #include "fd_sha512_gpu_private.h"
-#include "fd_poh_gpu_private.h"
-#include "fd_bmtree_gpu_private.h"
+#include "fd_ed25519_gpu_unit.h"
 
 #define FD_GPU_DEPTH_DEFAULT 3
 #define FD_GPU_DEPTH_MAX     8
@@ -124,6 +123,14 @@ static int fd_event_wait( hipEvent_t ev, long timeout_ns ) {
     return FD_ED25519_ERR_GPU;
   }
   return FD_ED25519_ERR_GPU;
+}
+
+/* fd_event_wait for the side units, within the engine's timeout: the text names the unit */
+int fd_ed25519_gpu_unit_wait( fd_ed25519_gpu_t * g, hipEvent_t ev, char const * who ) {
+  long to = fd_ed25519_gpu_timeout( g );
+  int r = fd_wait_query( fd_event_query, (void *)ev, FD_POLL_SPIN_NS, to );
+  if( r == 0 ) snprintf( fd_gpu_err, sizeof(fd_gpu_err), "%s wait: batch not complete after %ld ms", who, to / 1000000L );
+  return r == 1 ? 0 : FD_ED25519_ERR_GPU;
 }
 
 /* Self-test of the bounded wait without a device (tests/test_abi.py): a
@@ -242,20 +249,18 @@ struct fd_ed25519_gpu {
   /* transaction batches on the ring (under the ring lock) */
   unsigned long txn_ring_allocs;  /* slots whose transaction scratch was allocated (fd_ed25519_gpu_txn_ring_allocs) */
   hipEvent_t    txn_ring_ev[4];   /* fd_ed25519_gpu_txn_ring_timed: around the front kernel and the reduce */
-  fd_poh_gpu_ext_t poh;           /* Proof-of-History chains: fd_poh_gpu.cpp's own stream and scratch, made on first use */
-  fd_bmtree_gpu_ext_t bmtree;     /* Merkle trees: fd_bmtree_gpu.cpp's own stream and scratch, likewise */
+  fd_gpu_unit * unit[FD_GPU_UNIT_CNT];   /* side units (fd_ed25519_gpu_unit.h): Proof-of-History chains, Merkle trees; made on first use */
   fd_ring_lock  lock;
 };
 
-extern "C" fd_poh_gpu_ext_t * fd_ed25519_gpu_poh_ext( fd_ed25519_gpu_t * g ) { return &g->poh; }
-extern "C" fd_bmtree_gpu_ext_t * fd_ed25519_gpu_bmtree_ext( fd_ed25519_gpu_t * g ) { return &g->bmtree; }
+fd_gpu_unit ** fd_ed25519_gpu_units( fd_ed25519_gpu_t * g ) { return g->unit; }
 
 static inline long fd_timeout( fd_ed25519_gpu_t const * g ) { return __atomic_load_n( &g->timeout_ns, __ATOMIC_RELAXED ); }
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if( e_ != hipSuccess ) { fd_gpu_fail( #call, e_ ); goto fail; } } while(0)
 
 extern "C" char const * fd_ed25519_gpu_last_error( void ) { return fd_gpu_err; }
-/* for the host units outside this file (fd_poh_gpu.cpp, fd_bmtree_gpu.cpp) */
+/* for the host units outside this file (fd_ed25519_gpu_unit.cpp) */
 extern "C" void fd_ed25519_gpu_set_error( char const * what ) { snprintf( fd_gpu_err, sizeof(fd_gpu_err), "%s", what ); }
 
 extern "C" int fd_ed25519_gpu_device_cnt( void ) {
@@ -481,8 +486,7 @@ extern "C" void fd_ed25519_gpu_delete( fd_ed25519_gpu_t * g ) {
       return;
     }
   }
-  if( g->poh.fini ) g->poh.fini( g->poh.ctx );
-  if( g->bmtree.fini ) g->bmtree.fini( g->bmtree.ctx );
+  for( int k=0; k<FD_GPU_UNIT_CNT; k++ ) fd_gpu_unit_fini( g->unit[k] );
   for( int k=0; k<FD_REG_MAX; k++ ) if( g->reg[k].p ) fd_reg_release( (void *)g->reg[k].p );
   for( int s=0; s<g->depth; s++ ) {
     fd_ed25519_gpu_slot * sl = &g->slot[s];

@@ -1,10 +1,8 @@
 /* fd_poh_gpu.cpp -- host side of the Proof-of-History device path
    (include/fd_poh_gpu.h; the kernel is fd_k_poh, fd_poh_gpu_kernels.hip).
 
-   It hangs off the engine through one slot (fd_ed25519_gpu_poh_ext): a
-   stream, an event and scratch of its own, made at the first call and
-   freed by fd_ed25519_gpu_delete, so PoH batches neither share nor size
-   the verify path's rings and working sets.
+   It is a side unit of the engine (fd_ed25519_gpu_unit.h); its own state
+   is the chunk and the lane-order switch.
 
    The packed call orders the lanes by n descending.  Each wave then holds
    chains of about one length, the long chains start in the first launch,
@@ -17,13 +15,11 @@
    mixin field of its device copy, and a gate kernel marks the entries
    whose leaves cannot be used so that fd_k_poh refuses them unhashed. */
 
-#include <stdio.h>
 #include <string.h>
-#include <time.h>
 #include <algorithm>
 #include <functional>
-#include <mutex>
 #include <vector>
+#include "fd_ed25519_gpu_unit.h"
 #include "fd_poh_gpu_private.h"
 #include "fd_bmtree_gpu_private.h"
 
@@ -34,23 +30,21 @@
 #define FD_POH_ENT_SZ     sizeof(fd_poh_gpu_entry_t)
 #define FD_POH_ROW_SZ     (4UL*FD_POH_ROW_WORDS)
 
-struct fd_poh_ctx {
-  fd_ed25519_gpu_t * gpu;
-  int           device;
-  std::mutex    lock;        /* one packed call at a time: they share the scratch */
-  hipStream_t   stream;
-  hipEvent_t    done;
-  unsigned long cap;         /* entries the scratch holds */
-  uint8_t *     d_buf;       /* entries | order | codes | states | work rows, each for the call's n rounded up to 4 */
-  uint8_t *     h_in;        /* pinned: entries | order */
-  uint8_t *     h_out;       /* pinned: codes | states */
-  unsigned long chunk;       /* hashes per lane per launch */
-  int           nosort;      /* experiments (fd_poh_gpu_debug_set_sort): the packed call keeps the caller's lane order */
-  int           busy;        /* a call gave up waiting: `done` has not been seen complete since */
-  unsigned long t_cap, t_in_cap;   /* the entries call's trees: bytes of d_tree and h_tree */
-  uint8_t *     d_tree;      /* first | leaves | blob | tree codes | tree work */
-  uint8_t *     h_tree;      /* pinned: first | leaves | blob */
+struct __attribute__((visibility("hidden"))) fd_poh_ctx : fd_gpu_unit {
+  unsigned long chunk = FD_POH_GPU_CHUNK_DEFAULT;   /* hashes per lane per launch */
+  int           nosort = 0;  /* experiments (fd_poh_gpu_debug_set_sort): the packed call keeps the caller's lane order */
 };
+
+/* the unit's scratch */
+enum { FD_POH_D_BUF,     /* entries | order | codes | states | work rows, each for the call's n rounded up to 4 */
+       FD_POH_H_IN,      /* pinned: entries | order */
+       FD_POH_H_OUT,     /* pinned: codes | states */
+       FD_POH_D_TREE,    /* the entries call's trees: first | leaves | blob | tree codes | tree work */
+       FD_POH_H_TREE };  /* pinned: first | leaves | blob */
+
+static inline fd_poh_ctx * fd_poh_ctx_get( fd_ed25519_gpu_t * gpu ) {
+  return fd_gpu_unit_get<fd_poh_ctx>( gpu, FD_GPU_UNIT_POH, "poh" );
+}
 
 /* the leaves of fd_poh_gpu_verify_entries_packed */
 struct fd_poh_trees {
@@ -60,114 +54,7 @@ struct fd_poh_trees {
   unsigned long                blob_sz, leaf_max, n_leaves;
 };
 
-static int fd_poh_fail( char const * what, hipError_t e ) {
-  char buf[256];
-  snprintf( buf, sizeof(buf), "%s: %s", what, hipGetErrorString( e ) );
-  fd_ed25519_gpu_set_error( buf );
-  return FD_ED25519_ERR_GPU;
-}
-
-static inline long fd_poh_now_ns( void ) {
-  struct timespec t; clock_gettime( CLOCK_MONOTONIC, &t );
-  return (long)t.tv_sec * 1000000000L + (long)t.tv_nsec;
-}
-
-/* the engine's bounded wait: spin for 20 ms, then a query every ~50 us
-   until the engine's timeout (< 0: none) */
-static int fd_poh_wait( fd_poh_ctx * c ) {
-  long to = fd_ed25519_gpu_timeout( c->gpu ), t0 = fd_poh_now_ns();
-  for(;;) {
-    hipError_t e = hipEventQuery( c->done );
-    if( e == hipSuccess ) return 0;
-    if( e != hipErrorNotReady ) return fd_poh_fail( "hipEventQuery", e );
-    long dt = fd_poh_now_ns() - t0;
-    if( to >= 0 && dt > to ) {
-      char buf[128];
-      snprintf( buf, sizeof(buf), "poh wait: batch not complete after %ld ms", to / 1000000L );
-      fd_ed25519_gpu_set_error( buf );
-      return FD_ED25519_ERR_GPU;
-    }
-    if( dt <= 20000000L ) __builtin_ia32_pause();
-    else { struct timespec ts = { 0, 50000L }; nanosleep( &ts, NULL ); }
-  }
-}
-
-static void fd_poh_free_scratch( fd_poh_ctx * c ) {
-  if( c->d_buf ) hipFree( c->d_buf );
-  if( c->h_in  ) hipHostFree( c->h_in );
-  if( c->h_out ) hipHostFree( c->h_out );
-  if( c->d_tree ) hipFree( c->d_tree );
-  if( c->h_tree ) hipHostFree( c->h_tree );
-  c->d_buf = c->h_in = c->h_out = c->d_tree = c->h_tree = NULL; c->cap = c->t_cap = c->t_in_cap = 0UL;
-}
-
-static inline unsigned long fd_poh_r16( unsigned long n ) { return ( n + 15UL ) & ~15UL; }
-
-static int fd_poh_ensure_trees( fd_poh_ctx * c, unsigned long d_sz, unsigned long in_sz ) {
-  hipError_t e = hipSuccess;
-  if( d_sz > c->t_cap ) {
-    if( c->d_tree ) hipFree( c->d_tree );
-    c->d_tree = NULL; c->t_cap = 0UL;
-    unsigned long cap = fd_poh_r16( d_sz + d_sz/8UL );
-    e = hipMalloc( (void **)&c->d_tree, cap );
-    if( e == hipSuccess ) c->t_cap = cap;
-  }
-  if( e == hipSuccess && in_sz > c->t_in_cap ) {
-    if( c->h_tree ) hipHostFree( c->h_tree );
-    c->h_tree = NULL; c->t_in_cap = 0UL;
-    unsigned long cap = fd_poh_r16( in_sz + in_sz/8UL );
-    e = hipHostMalloc( (void **)&c->h_tree, cap, hipHostMallocDefault );
-    if( e == hipSuccess ) c->t_in_cap = cap;
-  }
-  if( e != hipSuccess ) return fd_poh_fail( "poh tree scratch", e );
-  return 0;
-}
-
-/* fd_ed25519_gpu_delete: the engine's own streams have drained.  If ours
-   does not within the engine's timeout, the scratch is leaked rather than
-   freed under a running kernel. */
-static void fd_poh_fini( void * p ) {
-  fd_poh_ctx * c = (fd_poh_ctx *)p;
-  hipSetDevice( c->device );
-  if( hipEventRecord( c->done, c->stream ) != hipSuccess || fd_poh_wait( c ) ) return;
-  fd_poh_free_scratch( c );
-  hipEventDestroy( c->done );
-  hipStreamDestroy( c->stream );
-  delete c;
-}
-
-static std::mutex fd_poh_make_lock;
-
-static fd_poh_ctx * fd_poh_ctx_get( fd_ed25519_gpu_t * g ) {
-  fd_poh_gpu_ext_t * x = fd_ed25519_gpu_poh_ext( g );
-  std::lock_guard<std::mutex> guard( fd_poh_make_lock );
-  if( x->ctx ) return (fd_poh_ctx *)x->ctx;
-  fd_poh_ctx * c = new fd_poh_ctx();
-  c->gpu = g; c->device = fd_ed25519_gpu_device( g ); c->chunk = FD_POH_GPU_CHUNK_DEFAULT;
-  hipError_t e = hipSetDevice( c->device );
-  if( e == hipSuccess ) e = hipStreamCreateWithFlags( &c->stream, hipStreamNonBlocking );
-  if( e == hipSuccess ) {
-    e = hipEventCreateWithFlags( &c->done, hipEventDisableTiming );
-    if( e != hipSuccess ) hipStreamDestroy( c->stream );
-  }
-  if( e != hipSuccess ) { fd_poh_fail( "poh stream", e ); delete c; return NULL; }
-  x->ctx = c; x->fini = fd_poh_fini;
-  return c;
-}
-
 static inline unsigned long fd_poh_r4( unsigned long n ) { return ( n + 3UL ) & ~3UL; }
-
-static int fd_poh_ensure( fd_poh_ctx * c, unsigned long n4 ) {
-  if( n4 <= c->cap ) return 0;
-  fd_poh_free_scratch( c );
-  unsigned long cap = ( n4 + 1023UL ) & ~1023UL;
-  hipError_t e = hipMalloc( (void **)&c->d_buf, cap * ( FD_POH_ENT_SZ + 4UL + 4UL + 32UL + FD_POH_ROW_SZ ) );
-  if( e == hipSuccess ) e = hipHostMalloc( (void **)&c->h_in,  cap * ( FD_POH_ENT_SZ + 4UL ), hipHostMallocDefault );
-  if( e == hipSuccess ) e = hipHostMalloc( (void **)&c->h_out, cap * ( 4UL + 32UL ),          hipHostMallocDefault );
-  if( e != hipSuccess ) { fd_poh_free_scratch( c ); return fd_poh_fail( "poh scratch", e ); }
-  c->cap = cap;
-  return 0;
-}
 
 static inline int fd_poh_entry_ok( fd_poh_gpu_entry_t const * e, unsigned long n_max ) {
   return !( e->flags & ~FD_POH_GPU_MIXIN ) && !e->_pad && e->n <= n_max;
@@ -184,8 +71,6 @@ FD_EXPORT unsigned long fd_poh_gpu_work_sz( unsigned long n ) { return ( n ? n :
 
 FD_EXPORT int fd_poh_gpu_debug_set_chunk( fd_ed25519_gpu_t * gpu, unsigned long C ) {
   if( C > FD_POH_CHUNK_MAX ) return FD_ED25519_ERR_ARG;
-  if( !gpu ) gpu = fd_ed25519_gpu_default();
-  if( !gpu ) return FD_ED25519_ERR_GPU;
   fd_poh_ctx * c = fd_poh_ctx_get( gpu );
   if( !c ) return FD_ED25519_ERR_GPU;
   std::lock_guard<std::mutex> guard( c->lock );
@@ -194,8 +79,6 @@ FD_EXPORT int fd_poh_gpu_debug_set_chunk( fd_ed25519_gpu_t * gpu, unsigned long 
 }
 
 FD_EXPORT int fd_poh_gpu_debug_set_sort( fd_ed25519_gpu_t * gpu, int on ) {
-  if( !gpu ) gpu = fd_ed25519_gpu_default();
-  if( !gpu ) return FD_ED25519_ERR_GPU;
   fd_poh_ctx * c = fd_poh_ctx_get( gpu );
   if( !c ) return FD_ED25519_ERR_GPU;
   std::lock_guard<std::mutex> guard( c->lock );
@@ -204,8 +87,7 @@ FD_EXPORT int fd_poh_gpu_debug_set_sort( fd_ed25519_gpu_t * gpu, int on ) {
 }
 
 FD_EXPORT unsigned long fd_poh_gpu_chunk( fd_ed25519_gpu_t * gpu ) {
-  if( !gpu ) gpu = fd_ed25519_gpu_default();
-  fd_poh_ctx * c = gpu ? fd_poh_ctx_get( gpu ) : NULL;
+  fd_poh_ctx * c = fd_poh_ctx_get( gpu );
   if( !c ) return 0UL;
   std::lock_guard<std::mutex> guard( c->lock );
   return c->chunk;
@@ -216,8 +98,6 @@ static int fd_poh_packed( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_en
                           unsigned long n_max, int * out, void * state_out_opt, fd_poh_trees const * tr ) {
   if( n > FD_POH_N_MAX || ( n && ( !entries || !out ) ) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
-  if( !gpu ) gpu = fd_ed25519_gpu_default();
-  if( !gpu ) return FD_ED25519_ERR_GPU;
   fd_poh_ctx * c = fd_poh_ctx_get( gpu );
   if( !c ) return FD_ED25519_ERR_GPU;
   std::lock_guard<std::mutex> guard( c->lock );
@@ -250,51 +130,45 @@ static int fd_poh_packed( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_en
     for( unsigned long i=0; i<n; i++ ) len[i] = eff( order[i] );
   }
 
-  hipError_t e = hipSetDevice( c->device );
-  if( e != hipSuccess ) return fd_poh_fail( "hipSetDevice", e );
-  if( c->busy ) {                       /* an earlier call's launches may still be using the scratch */
-    if( fd_poh_wait( c ) ) return FD_ED25519_ERR_GPU;
-    c->busy = 0;
-  }
-  unsigned long n4 = fd_poh_r4( n );
-  int err = fd_poh_ensure( c, n4 );
+  int err = fd_gpu_unit_begin( c );
   if( err ) return err;
-
+  unsigned long n4     = fd_poh_r4( n );
   unsigned long in_sz  = n4 * ( FD_POH_ENT_SZ + 4UL );
   unsigned long out_sz = n4 * ( state_out_opt ? 36UL : 4UL );
-  uint8_t * d_ent   = c->d_buf;
+  if( (err = fd_gpu_unit_grow( c, FD_POH_D_BUF, 0, n4 * ( FD_POH_ENT_SZ + 4UL + 4UL + 32UL + FD_POH_ROW_SZ ) )) ||
+      (err = fd_gpu_unit_grow( c, FD_POH_H_IN,  1, in_sz )) ||
+      (err = fd_gpu_unit_grow( c, FD_POH_H_OUT, 1, n4 * 36UL )) ) return err;
+  uint8_t * h_in = c->buf[FD_POH_H_IN].p, * h_out = c->buf[FD_POH_H_OUT].p;
+  uint8_t * d_ent   = c->buf[FD_POH_D_BUF].p;
   uint8_t * d_order = d_ent   + n4 * FD_POH_ENT_SZ;
   uint8_t * d_out   = d_order + n4 * 4UL;
   uint8_t * d_state = d_out   + n4 * 4UL;
   uint8_t * d_work  = d_state + n4 * 32UL;
-  memcpy( c->h_in, entries, n * FD_POH_ENT_SZ );
-  memcpy( c->h_in + n4 * FD_POH_ENT_SZ, order.data(), n * 4UL );
+  memcpy( h_in, entries, n * FD_POH_ENT_SZ );
+  memcpy( h_in + n4 * FD_POH_ENT_SZ, order.data(), n * 4UL );
 
   /* the trees' inputs, staged like the entries */
-  unsigned long first_sz = 0UL, leaf_sz = 0UL, t_in_sz = 0UL, tcode_sz = 0UL;
+  unsigned long first_sz = 0UL, leaf_sz = 0UL, t_in_sz = 0UL, tcode_sz = fd_gpu_r16( 4UL*n );
+  uint8_t * d_tree = NULL;
   if( tr && tr->n_leaves ) {
-    first_sz = fd_poh_r16( 4UL*( n + 1UL ) ); leaf_sz = fd_poh_r16( 8UL*tr->n_leaves ); tcode_sz = fd_poh_r16( 4UL*n );
-    t_in_sz  = first_sz + leaf_sz + fd_poh_r16( tr->blob_sz );
-    err = fd_poh_ensure_trees( c, t_in_sz + tcode_sz + fd_bmtree_gpu_work_sz( n, tr->n_leaves ), t_in_sz );
-    if( err ) return err;
-    uint32_t * h_first = (uint32_t *)c->h_tree;
-    unsigned long run = 0UL;
-    for( unsigned long i=0; i<n; i++ ) { h_first[i] = (uint32_t)run; run += tr->leaf_cnt[i]; }
-    h_first[n] = (uint32_t)run;
-    memcpy( c->h_tree + first_sz, tr->leaves, 8UL*tr->n_leaves );
-    if( tr->blob_sz ) memcpy( c->h_tree + first_sz + leaf_sz, tr->blob, tr->blob_sz );
+    fd_bmtree_staged_t in = fd_bmtree_gpu_stage( NULL, n, tr->leaf_cnt, tr->n_leaves, tr->leaves, tr->blob, tr->blob_sz );
+    first_sz = in.first_sz; leaf_sz = in.leaf_sz; t_in_sz = first_sz + leaf_sz + in.blob_sz;
+    if( (err = fd_gpu_unit_grow( c, FD_POH_D_TREE, 0, t_in_sz + tcode_sz + fd_bmtree_gpu_work_sz( n, tr->n_leaves ) )) ||
+        (err = fd_gpu_unit_grow( c, FD_POH_H_TREE, 1, t_in_sz )) ) return err;
+    d_tree = c->buf[FD_POH_D_TREE].p;
+    fd_bmtree_gpu_stage( c->buf[FD_POH_H_TREE].p, n, tr->leaf_cnt, tr->n_leaves, tr->leaves, tr->blob, tr->blob_sz );
   }
 
-  e = hipMemcpyAsync( d_ent, c->h_in, in_sz, hipMemcpyHostToDevice, c->stream );
-  if( e == hipSuccess && t_in_sz ) e = hipMemcpyAsync( c->d_tree, c->h_tree, t_in_sz, hipMemcpyHostToDevice, c->stream );
+  hipError_t e = hipMemcpyAsync( d_ent, h_in, in_sz, hipMemcpyHostToDevice, c->stream );
+  if( e == hipSuccess && t_in_sz ) e = hipMemcpyAsync( d_tree, c->buf[FD_POH_H_TREE].p, t_in_sz, hipMemcpyHostToDevice, c->stream );
   if( e == hipSuccess && t_in_sz ) {    /* roots into the mixins, then the gate, ahead of the first chain launch */
-    uint8_t * d_tcodes = c->d_tree + t_in_sz;
-    int r = fd_bmtree_gpu_roots_dev_flags( gpu, 32U, FD_BMTREE_GPU_SKIP_EMPTY, n, (uint32_t const *)c->d_tree, tr->n_leaves,
-                                           (fd_bmtree_gpu_leaf_t const *)( c->d_tree + first_sz ), c->d_tree + first_sz + leaf_sz,
+    uint8_t * d_tcodes = d_tree + t_in_sz;
+    int r = fd_bmtree_gpu_roots_dev_flags( c->gpu, 32U, FD_BMTREE_GPU_SKIP_EMPTY, n, (uint32_t const *)d_tree, tr->n_leaves,
+                                           (fd_bmtree_gpu_leaf_t const *)( d_tree + first_sz ), d_tree + first_sz + leaf_sz,
                                            tr->blob_sz, tr->leaf_max, d_ent + 32UL, FD_POH_ENT_SZ, (int *)d_tcodes, d_tcodes + tcode_sz,
                                            c->stream );
     if( r ) e = hipErrorLaunchFailure;
-    else    e = fd_bmtree_gpu_poh_gate_launch( (uint32_t)n, (uint32_t const *)c->d_tree, (int32_t const *)d_tcodes,
+    else    e = fd_bmtree_gpu_poh_gate_launch( (uint32_t)n, (uint32_t const *)d_tree, (int32_t const *)d_tcodes,
                                                (fd_poh_gpu_entry_t *)d_ent, c->stream );
   }
   unsigned long lanes = n;
@@ -306,15 +180,11 @@ static int fd_poh_packed( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_en
     e = fd_poh_gpu_launch( (uint32_t)lanes, j == 0UL, (uint32_t)C, n_max, (fd_poh_gpu_entry_t const *)d_ent, (uint32_t const *)d_order,
                            (uint32_t *)d_work, (int32_t *)d_out, state_out_opt ? d_state : NULL, c->stream );
   }
-  if( e == hipSuccess ) e = hipMemcpyAsync( c->h_out, d_out, out_sz, hipMemcpyDeviceToHost, c->stream );
-  /* whatever was queued is waited for, also after a failed enqueue */
-  hipError_t e2 = hipEventRecord( c->done, c->stream );
-  if( e2 != hipSuccess ) { c->busy = 1; return fd_poh_fail( "hipEventRecord", e2 ); }
-  if( fd_poh_wait( c ) ) { c->busy = 1; return FD_ED25519_ERR_GPU; }
-  if( e != hipSuccess ) return fd_poh_fail( "poh launch", e );
+  if( e == hipSuccess ) e = hipMemcpyAsync( h_out, d_out, out_sz, hipMemcpyDeviceToHost, c->stream );
+  if( (err = fd_gpu_unit_finish( c, e )) ) return err;
 
-  memcpy( out, c->h_out, n * 4UL );
-  if( state_out_opt ) memcpy( state_out_opt, c->h_out + n4 * 4UL, n * 32UL );
+  memcpy( out, h_out, n * 4UL );
+  if( state_out_opt ) memcpy( state_out_opt, h_out + n4 * 4UL, n * 32UL );
   return 0;
 }
 
@@ -337,7 +207,7 @@ FD_EXPORT int fd_poh_gpu_verify_entries_packed( fd_ed25519_gpu_t * gpu, unsigned
 
 FD_EXPORT unsigned long fd_poh_gpu_entries_work_sz( unsigned long n, unsigned long n_leaves ) {
   unsigned long w = fd_bmtree_gpu_work_sz( n, n_leaves );
-  return w ? fd_poh_r16( 4UL*( n ? n : 1UL ) ) + w : 0UL;
+  return w ? fd_gpu_r16( 4UL*( n ? n : 1UL ) ) + w : 0UL;
 }
 
 FD_EXPORT int fd_poh_gpu_verify_entries_dev( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t * d_entries, unsigned long n_max,
@@ -349,24 +219,22 @@ FD_EXPORT int fd_poh_gpu_verify_entries_dev( fd_ed25519_gpu_t * gpu, unsigned lo
   if( ( (uintptr_t)d_entries & 7UL ) || blob_sz > 0xffffffffUL || !leaf_max || n_leaves > FD_BMTREE_GPU_LEAVES_MAX ) return FD_ED25519_ERR_ARG;
   if( n_leaves && ( !d_leaves || ( blob_sz && !d_blob ) ) ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
-  if( !gpu ) gpu = fd_ed25519_gpu_default();
-  if( !gpu ) return FD_ED25519_ERR_GPU;
   fd_poh_ctx * c = fd_poh_ctx_get( gpu );
   if( !c ) return FD_ED25519_ERR_GPU;
   { std::lock_guard<std::mutex> guard( c->lock );
     if( fd_poh_launches( n_max, c->chunk ) > FD_POH_GPU_LAUNCH_MAX ) return FD_ED25519_ERR_ARG; }   /* before anything is queued */
   hipError_t e = hipSetDevice( c->device );
-  if( e != hipSuccess ) return fd_poh_fail( "hipSetDevice", e );
+  if( e != hipSuccess ) return fd_gpu_unit_fail( "hipSetDevice", e );
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   if( n_leaves ) {
     uint8_t * d_tcodes = (uint8_t *)d_tree_work;
-    int r = fd_bmtree_gpu_roots_dev_flags( gpu, 32U, FD_BMTREE_GPU_SKIP_EMPTY, n, d_first, n_leaves, d_leaves, d_blob, blob_sz, leaf_max,
-                                           (uint8_t *)d_entries + 32UL, FD_POH_ENT_SZ, (int *)d_tcodes, d_tcodes + fd_poh_r16( 4UL*n ), st );
+    int r = fd_bmtree_gpu_roots_dev_flags( c->gpu, 32U, FD_BMTREE_GPU_SKIP_EMPTY, n, d_first, n_leaves, d_leaves, d_blob, blob_sz, leaf_max,
+                                           (uint8_t *)d_entries + 32UL, FD_POH_ENT_SZ, (int *)d_tcodes, d_tcodes + fd_gpu_r16( 4UL*n ), st );
     if( r ) return r;
     e = fd_bmtree_gpu_poh_gate_launch( (uint32_t)n, d_first, (int32_t const *)d_tcodes, d_entries, st );
-    if( e != hipSuccess ) return fd_poh_fail( "poh gate launch", e );
+    if( e != hipSuccess ) return fd_gpu_unit_fail( "poh gate launch", e );
   }
-  return fd_poh_gpu_verify_dev( gpu, n, d_entries, n_max, d_out, d_state_out_opt, d_work, st );
+  return fd_poh_gpu_verify_dev( c->gpu, n, d_entries, n_max, d_out, d_state_out_opt, d_work, st );
 }
 
 FD_EXPORT int fd_poh_gpu_verify_dev( fd_ed25519_gpu_t * gpu, unsigned long n, fd_poh_gpu_entry_t const * d_entries, unsigned long n_max,
@@ -374,8 +242,6 @@ FD_EXPORT int fd_poh_gpu_verify_dev( fd_ed25519_gpu_t * gpu, unsigned long n, fd
   if( n > FD_POH_N_MAX || ( n && ( !d_entries || !d_out || !d_work ) ) ) return FD_ED25519_ERR_ARG;
   if( ( (uintptr_t)d_work | (uintptr_t)d_state_out_opt ) & 15UL ) return FD_ED25519_ERR_ARG;
   if( !n ) return 0;
-  if( !gpu ) gpu = fd_ed25519_gpu_default();
-  if( !gpu ) return FD_ED25519_ERR_GPU;
   fd_poh_ctx * c = fd_poh_ctx_get( gpu );
   if( !c ) return FD_ED25519_ERR_GPU;
   unsigned long C;
@@ -383,12 +249,12 @@ FD_EXPORT int fd_poh_gpu_verify_dev( fd_ed25519_gpu_t * gpu, unsigned long n, fd
   unsigned long launches = fd_poh_launches( n_max, C );
   if( launches > FD_POH_GPU_LAUNCH_MAX ) return FD_ED25519_ERR_ARG;
   hipError_t e = hipSetDevice( c->device );
-  if( e != hipSuccess ) return fd_poh_fail( "hipSetDevice", e );
+  if( e != hipSuccess ) return fd_gpu_unit_fail( "hipSetDevice", e );
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   for( unsigned long j=0; j<launches; j++ ) {
     e = fd_poh_gpu_launch( (uint32_t)n, j == 0UL, (uint32_t)C, n_max, d_entries, NULL, (uint32_t *)d_work, (int32_t *)d_out,
                            (uint8_t *)d_state_out_opt, st );
-    if( e != hipSuccess ) return fd_poh_fail( "poh launch", e );
+    if( e != hipSuccess ) return fd_gpu_unit_fail( "poh launch", e );
   }
   return 0;
 }

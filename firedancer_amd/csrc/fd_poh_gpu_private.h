@@ -1,8 +1,8 @@
 #ifndef HEADER_fd_poh_gpu_private_h
 #define HEADER_fd_poh_gpu_private_h
 
-/* fd_poh_gpu_private.h -- between fd_poh_gpu.cpp (host side), the kernel
-   unit fd_poh_gpu_kernels.hip and the engine (fd_ed25519_gpu_host.cpp). */
+/* fd_poh_gpu_private.h -- between fd_poh_gpu.cpp (host side) and the
+   kernel unit fd_poh_gpu_kernels.hip. */
 
 #include <hip/hip_runtime.h>
 #include "fd_poh_gpu.h"
@@ -22,13 +22,5 @@
 extern "C" hipError_t fd_poh_gpu_launch( uint32_t lanes, uint32_t first, uint32_t chunk, uint64_t n_max,
                                          fd_poh_gpu_entry_t const * ent, uint32_t const * order, uint32_t * work,
                                          int32_t * out, uint8_t * state_out, hipStream_t stream );
-
-/* The engine's slot for the PoH host side: created on first use by
-   fd_poh_gpu.cpp; fd_ed25519_gpu_delete calls fini( ctx ) once its own
-   streams have drained. */
-typedef struct { void * ctx; void (*fini)( void * ctx ); } fd_poh_gpu_ext_t;
-extern "C" fd_poh_gpu_ext_t * fd_ed25519_gpu_poh_ext( fd_ed25519_gpu_t * gpu );
-/* what fd_ed25519_gpu_last_error returns on this thread */
-extern "C" void fd_ed25519_gpu_set_error( char const * what );
 
 #endif /* HEADER_fd_poh_gpu_private_h */

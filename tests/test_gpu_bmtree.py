@@ -8,6 +8,7 @@ import pytest
 
 import bmtree_grid as bg
 import firedancer_amd as fa
+from conftest import P
 
 pytestmark = pytest.mark.gpu
 
@@ -190,5 +191,32 @@ def test_scratch_growth_and_second_engine():
         cnt, leaves, blob, want = _count_grid(32)
         got, codes = e.bmtree_roots(32, cnt, leaves, blob, 4097)
         assert (codes == 0).all() and (got == want).all()
+    finally:
+        e.close()
+
+
+def test_timeout_writes_nothing_and_engine_recovers():
+    """a packed call that gives up waiting writes nothing, and the next one
+    waits the abandoned launches out before it uses the scratch"""
+    e = fa.Engine(0, 1 << 10, 1 << 16)
+    try:
+        cnt, leaves, blob = bg.sig_batch([16] * 4096, 12)        # 65,536 leaves, a 4 MiB blob
+        want, want_codes = bg.model(32, cnt, leaves, blob, 16)
+        assert (want_codes == 0).all()
+        roots = np.full((4096, 32), 0x5A, np.uint8)
+        codes = np.full(4096, 77, np.int32)
+        e.timeout_ns = 1_000                                     # the 4 MiB copy alone takes some 65 us
+        r = fa.lib().fd_bmtree_gpu_roots_packed(e._h, 32, 0, 4096, P(cnt), P(leaves), P(blob), blob.nbytes, 16, P(roots), P(codes))
+        assert r == fa.ERR_GPU
+        assert "not complete" in fa.last_error()
+        assert (roots == 0x5A).all() and (codes == 77).all()
+        e.timeout_ns = 10_000_000_000
+        got, got_codes = e.bmtree_roots(32, cnt, leaves, blob, 16)
+        assert (got_codes == 0).all() and (got == want).all()
+        # a smaller call after a larger one on a unit that was busy
+        cnt, leaves, blob = bg.sig_batch([3, 1, 2], 11)
+        want, _ = bg.model(32, cnt, leaves, blob, 3)
+        got, got_codes = e.bmtree_roots(32, cnt, leaves, blob, 3)
+        assert (got_codes == 0).all() and (got == want).all()
     finally:
         e.close()

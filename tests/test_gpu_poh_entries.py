@@ -11,6 +11,7 @@ import pytest
 import bmtree_grid as bg
 import firedancer_amd as fa
 import poh_grid as pg
+from conftest import P
 
 pytestmark = pytest.mark.gpu
 
@@ -120,12 +121,12 @@ def test_entries_dev(engine, chunk, C, own_stream):
         assert (after[f] == ent[f]).all(), f
 
 
-def _small(rng, n_leaf_list):
+def _small(rng, n_leaf_list, n_hash=None):
     trees = [[rng.bytes(64) for _ in range(k)] for k in n_leaf_list]
     cnt, leaves, blob = bg.pack(trees)
     ent = np.zeros(len(trees), fa.POH_ENTRY_DTYPE)
     for i, t in enumerate(trees):
-        pg.entry(ent[i], rng.bytes(32), 3 + i % 4, bg.root(t, 32) if t else (rng.bytes(32) if i & 1 else None))
+        pg.entry(ent[i], rng.bytes(32), n_hash or 3 + i % 4, bg.root(t, 32) if t else (rng.bytes(32) if i & 1 else None))
     return trees, cnt, leaves, blob, ent
 
 
@@ -167,3 +168,29 @@ def test_leaves_without_flag_refused_trees_and_n_max(engine, chunk):
     got, st = engine.poh_verify_entries(ent, 6, cnt, leaves, blob, 7, states=True)
     assert (got == exp).all()                          # the neighbours are unaffected
     assert (st == true).all()
+
+
+def test_timeout_then_recovery():
+    """a packed entries call that gives up waiting writes nothing, and the
+    next one waits the abandoned launches out before it uses the scratch"""
+    e = fa.Engine(0, 1 << 10, 1 << 16)
+    try:
+        n_hash = 40000
+        # one entry of three signature leaves, 64 times: the chain is hashed here once
+        _, cnt, leaves, blob, ent = _small(np.random.default_rng(23), [3], n_hash)
+        assert ent[0]["flags"] == fa.POH_MIXIN
+        cnt, leaves, ent = np.repeat(cnt, 64), np.tile(leaves, 64), np.repeat(ent, 64)
+        e.poh_chunk = 64                          # 625 launches behind the trees
+        out = np.full(64, 77, np.int32)
+        st = np.full((64, 32), 0x55, np.uint8)
+        e.timeout_ns = 1_000_000
+        r = fa.lib().fd_poh_gpu_verify_entries_packed(e._h, 64, P(ent), n_hash, P(out), P(st), P(cnt), P(leaves), P(blob),
+                                                      blob.nbytes, 3)
+        assert r == fa.ERR_GPU
+        assert "not complete" in fa.last_error()
+        assert (out == 77).all() and (st == 0x55).all()
+        e.timeout_ns = 10_000_000_000
+        got, st2 = e.poh_verify_entries(ent, n_hash, cnt, leaves, blob, 3, states=True)
+        assert (got == 0).all() and (st2 == ent["expect"]).all()
+    finally:
+        e.close()
