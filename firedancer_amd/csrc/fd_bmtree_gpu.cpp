@@ -51,18 +51,6 @@ static inline int fd_bmtree_args_ok( unsigned width, unsigned flags, unsigned al
          blob_sz <= 0xffffffffUL && leaf_max >= 1UL;
 }
 
-/* the plan of a call and its merge lanes: lanes[l] bounds layer l+1 */
-static void fd_bmtree_plan_make( fd_bmtree_plan_t * p, unsigned width, unsigned flags, unsigned long n_trees, unsigned long n_leaves,
-                                 unsigned long blob_sz, unsigned long leaf_max, uint8_t * d_work, uint32_t lanes[32] ) {
-  memset( p, 0, sizeof(*p) );
-  p->width = width; p->flags = flags; p->T = (uint32_t)n_trees; p->N = (uint32_t)n_leaves;
-  p->leaf_max = (uint32_t)( leaf_max < 0xffffffffUL ? leaf_max : 0xffffffffUL );
-  p->blob_sz  = (uint32_t)blob_sz;
-  p->L = fd_bmtree_ceil_log2( leaf_max < n_leaves ? leaf_max : n_leaves );
-  fd_bmtree_plan_layout( p, d_work );
-  for( uint32_t l=0U; l<p->L; l++ ) lanes[l] = (uint32_t)fd_bmtree_layer_bound( n_trees, n_leaves, l + 1U );
-}
-
 extern "C" int fd_bmtree_gpu_roots_dev_flags( fd_ed25519_gpu_t * gpu, unsigned width, unsigned flags, unsigned long n_trees,
                                               uint32_t const * d_first, unsigned long n_leaves, fd_bmtree_gpu_leaf_t const * d_leaves,
                                               void const * d_blob, unsigned long blob_sz, unsigned long leaf_max, void * d_roots,

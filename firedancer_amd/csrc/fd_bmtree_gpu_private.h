@@ -5,6 +5,7 @@
    kernel unit fd_bmtree_gpu_kernels.hip and fd_poh_gpu.cpp (entries from
    leaves). */
 
+#include <string.h>
 #include <hip/hip_runtime.h>
 #include "fd_bmtree_gpu.h"
 #include "fd_poh_gpu.h"
@@ -71,6 +72,20 @@ static inline unsigned long fd_bmtree_plan_layout( fd_bmtree_plan_t * p, uint8_t
 static inline unsigned long fd_bmtree_layer_bound( unsigned long T, unsigned long N, uint32_t l ) {
   unsigned long act = N / ( ( 1UL << (l-1U) ) + 1UL );
   return ( N >> l ) + ( act < T ? act : T );
+}
+
+/* the plan of a call and its merge lanes: lanes[l] bounds layer l+1.  Here,
+   and not in fd_bmtree_gpu.cpp, so that tests/bmtree_plan_harness.cpp runs
+   the arithmetic the calls run. */
+static inline void fd_bmtree_plan_make( fd_bmtree_plan_t * p, unsigned width, unsigned flags, unsigned long n_trees, unsigned long n_leaves,
+                                        unsigned long blob_sz, unsigned long leaf_max, uint8_t * d_work, uint32_t lanes[32] ) {
+  memset( p, 0, sizeof(*p) );
+  p->width = width; p->flags = flags; p->T = (uint32_t)n_trees; p->N = (uint32_t)n_leaves;
+  p->leaf_max = (uint32_t)( leaf_max < 0xffffffffUL ? leaf_max : 0xffffffffUL );
+  p->blob_sz  = (uint32_t)blob_sz;
+  p->L = fd_bmtree_ceil_log2( leaf_max < n_leaves ? leaf_max : n_leaves );
+  fd_bmtree_plan_layout( p, d_work );
+  for( uint32_t l=0U; l<p->L; l++ ) lanes[l] = (uint32_t)fd_bmtree_layer_bound( n_trees, n_leaves, l + 1U );
 }
 
 /* Queues the whole call on stream: clear, check, the three offset kernels,

@@ -105,6 +105,54 @@ def test_roots_batch_grid(W, nthreads):
     assert (got_r == want_r).all()
 
 
+@pytest.mark.parametrize("T", [257, 1279])
+@pytest.mark.parametrize("W", [20, 32])
+def test_roots_batch_blocks_of_trees(W, T):
+    """the device tests' batches around the set-up blocks of 256 trees
+    (tests/test_gpu_bmtree_blocks.py), so that the yardstick is held to the
+    model on them too"""
+    for name in bg.block_variants(T):
+        cnt, leaves, blob = bg.block_batch(T, name)
+        want_r, want_c = bg.model(W, cnt, leaves, blob, bg.BLOCK_LEAF_MAX)
+        assert ((want_c != 0) == ((cnt == 0) | (cnt == 34))).all()
+        got_r, got_c = fa.bmtree_roots_batch(W, cnt, leaves, blob, bg.BLOCK_LEAF_MAX, 0, 5)
+        assert (got_c == want_c).all() and (got_r == want_r).all(), name
+
+
+@pytest.mark.parametrize("nodes", [False, True])
+@pytest.mark.parametrize("W", [20, 32])
+def test_roots_batch_tight_shapes(W, nodes):
+    """the shapes that meet the device call's lane bound and capacities"""
+    for k, counts in enumerate(bg.TIGHT_SHAPES):
+        cnt, leaves, blob = bg.tight_batch(counts, W, nodes, 600 + k)
+        for leaf_max in (max(counts), 1 << 30):
+            want_r, want_c = bg.model(W, cnt, leaves, blob, leaf_max, nodes)
+            got_r, got_c = fa.bmtree_roots_batch(W, cnt, leaves, blob, leaf_max, fa.BMTREE_LEAVES_ARE_NODES if nodes else 0, 3)
+            assert (want_c == 0).all() and (got_c == 0).all() and (got_r == want_r).all(), counts[:3]
+
+
+@pytest.mark.parametrize("nodes", [False, True])
+def test_model_refusals_rule_by_rule(nodes):
+    """the model's vectorised refusals against bg.refused, the header's rules one descriptor at a time"""
+    cnt, leaves, blob, leaf_max, bad = bg.refusal_batch(32, nodes)
+    first = np.concatenate([[0], np.cumsum(cnt)]).astype(int)
+    slow = [bg.refused(int(c), [(int(d["off"]), int(d["sz"])) for d in leaves[first[t]:first[t + 1]]], len(blob), leaf_max, 32, nodes)
+            for t, c in enumerate(cnt)]
+    assert np.nonzero(slow)[0].tolist() == bad
+    assert ((bg.model(32, cnt, leaves, blob, leaf_max, nodes)[1] != 0) == slow).all()
+
+
+def test_layer_helpers():
+    """bmtree_grid's shape helpers on cases done by hand"""
+    assert bg.layer_counts([5, 1, 0, 3], 5) == [3 + 2, 2 + 1, 1]
+    assert bg.layer_counts([5, 1, 0, 3], 4) == [2, 1]
+    assert bg.layer_counts([1, 0], 8) == []
+    assert bg.layer_bound(3, 15, 2) == 6 and bg.layer_bound(1, 3, 1) == 2 and bg.layer_bound(3, 35, 6) == 1
+    cnt, leaves, blob = bg.pool_batch([2, 0, 3], 20, 1)
+    assert blob.nbytes == 4096 * 20 and (leaves["sz"] == 20).all() and (leaves["off"] % 20 == 0).all() and len(leaves) == 5
+    assert len(set(leaves["off"].tolist())) == 5
+
+
 def test_roots_batch_bad_calls():
     L = fa.lib()
     cnt, leaves, blob = bg.sig_batch([2, 3], 6)

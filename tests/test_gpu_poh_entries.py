@@ -170,6 +170,122 @@ def test_leaves_without_flag_refused_trees_and_n_max(engine, chunk):
     assert (st == true).all()
 
 
+BIG = 1300
+SPECIAL = {0: "tick", 255: "noflag", 256: "size", 511: "blob", 512: "n_max", 1299: "blob_last"}
+
+
+@functools.lru_cache(maxsize=None)
+def _big_batch():
+    """1,300 entries, over six set-up blocks of 256 trees and six blocks of
+    the gate kernel, kinds and leaf counts cycling as in _batch, chains of
+    0..5 hashes, leaf_max 8 (so 9 leaves are refused), every 7th expect
+    flipped.  At entries 0, 255, 256, 511, 512 and 1,299, the first and the
+    last entry of a block: a tick, leaves without FD_POH_GPU_MIXIN, a tree
+    refused by size, trees refused by a descriptor past the blob (on the
+    first leaf, and on the call's last leaf), and n > n_max on an entry with
+    leaves.  Returns (entries, the same as Engine.poh_verify must see them:
+    the model's roots as mixins and _pad set where the gate sets it,
+    leaf_cnt, leaves, blob, codes, states, roots, gated, the trees' codes)."""
+    rng = np.random.default_rng(77)
+    n_leaf_of = {"tick": 0, "noflag": 3, "size": 9, "blob": 4, "n_max": 4, "blob_last": 5}
+    kinds, trees = [], []
+    for i in range(BIG):
+        kind = i % 3
+        n_leaf = (i // 3) % 10 if kind == 2 else 0
+        if kind == 2 and n_leaf == 0:
+            kind = 1
+        if i in SPECIAL:
+            n_leaf = n_leaf_of[SPECIAL[i]]
+            kind = 2 if n_leaf else 0
+        kinds.append(kind)
+        trees.append([rng.bytes(64) for _ in range(n_leaf)])
+    cnt, leaves, blob = bg.pack(trees, align_of=lambda k: 5 * k)
+    first = np.concatenate([[0], np.cumsum(cnt)]).astype(int)
+    leaves[first[511]]["off"] = len(blob) - 10
+    leaves[first[1300] - 1]["off"] = len(blob) - 63
+    roots, tcodes = bg.model(32, cnt, leaves, blob, 8)
+    ent = np.zeros(BIG, fa.POH_ENTRY_DTYPE)
+    ref = np.zeros(BIG, fa.POH_ENTRY_DTYPE)
+    codes = np.zeros(BIG, np.int32)
+    states = np.zeros((BIG, 32), np.uint8)
+    gated = np.zeros(BIG, bool)
+    for i in range(BIG):
+        n = (i * 5 + i // 9) % 6
+        start = rng.bytes(32)
+        mixin = None if kinds[i] == 0 else rng.bytes(32) if kinds[i] == 1 else roots[i].tobytes()
+        pg.entry(ref[i], start, n, mixin)
+        if i % 7 == 3:
+            ref[i]["expect"][int(rng.integers(32))] ^= 1 << int(rng.integers(8))
+        ent[i] = ref[i]
+        if kinds[i] != 1:
+            ent[i]["mixin"] = np.frombuffer(rng.bytes(32), np.uint8)
+        if SPECIAL.get(i) == "noflag":
+            ent[i]["flags"] = ref[i]["flags"] = 0
+        if SPECIAL.get(i) == "n_max":
+            ent[i]["n"] = ref[i]["n"] = 6
+        gated[i] = cnt[i] > 0 and (tcodes[i] != 0 or not ent[i]["flags"] & fa.POH_MIXIN)
+        if gated[i] or ent[i]["n"] > 5:
+            codes[i] = fa.ERR_ARG                    # refused unhashed: the state stays zero
+        else:
+            states[i] = np.frombuffer(pg.ref(start, n, mixin), np.uint8)
+            codes[i] = fa.POH_ERR_HASH if i % 7 == 3 else 0
+    ref["_pad"][gated] = 1
+    # the placement
+    assert cnt[0] == 0 and not ent[0]["flags"] and codes[0] == 0
+    assert cnt[255] == 3 and tcodes[255] == 0 and gated[255]
+    assert cnt[256] == 9 and tcodes[256] != 0 and gated[256]
+    assert 0 < cnt[511] <= 8 and tcodes[511] != 0 and 0 < cnt[1299] <= 8 and tcodes[1299] != 0
+    assert 0 < cnt[512] <= 8 and tcodes[512] == 0 and not gated[512] and codes[512] == fa.ERR_ARG
+    assert all(codes[i] == fa.ERR_ARG for i in SPECIAL if i) and set(cnt.tolist()) == set(range(10))
+    assert set(ent["n"][~gated].tolist()) == set(range(7)) and (codes == fa.POH_ERR_HASH).sum() > 150
+    return ent, ref, cnt, leaves, blob, codes, states, roots, gated, tcodes
+
+
+def test_entries_across_blocks_packed(engine, chunk):
+    ent, ref, cnt, leaves, blob, codes, states, _, _, _ = _big_batch()
+    chunk(2)
+    want_c, want_s = engine.poh_verify(ref, 5, states=True)
+    assert (want_c == codes).all() and (want_s == states).all()
+    before = ent.copy()
+    got_c, got_s = engine.poh_verify_entries(ent, 5, cnt, leaves, blob, 8, states=True)
+    assert (got_c == codes).all()
+    assert (got_s == states).all()
+    assert (ent == before).all()
+
+
+def test_entries_across_blocks_dev(engine, chunk):
+    import torch
+    ent, ref, cnt, leaves, blob, codes, states, roots, gated, tcodes = _big_batch()
+    chunk(2)
+    dev = torch.device("cuda", 0)
+    N = len(leaves)
+    first = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32)
+    d_ent = torch.from_numpy(ent.view(np.uint8).copy()).to(dev)
+    d_first = torch.from_numpy(first.view(np.int32).copy()).to(dev)
+    d_leaves = torch.from_numpy(leaves.view(np.uint8).copy()).to(dev)
+    d_blob = torch.from_numpy(blob.copy()).to(dev)
+    d_out = torch.full((BIG,), 77, dtype=torch.int32, device=dev)
+    d_st = torch.full((BIG, 32), 0x55, dtype=torch.uint8, device=dev)
+    d_work = torch.zeros(fa.poh_work_sz(BIG), dtype=torch.uint8, device=dev)
+    d_twork = torch.zeros(fa.poh_entries_work_sz(BIG, N), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    engine.poh_verify_entries_dev(BIG, d_ent.data_ptr(), 5, d_out.data_ptr(), d_st.data_ptr(), d_work.data_ptr(), d_first.data_ptr(), N,
+                                  d_leaves.data_ptr(), d_blob.data_ptr(), blob.nbytes, 8, d_twork.data_ptr())
+    torch.cuda.synchronize()
+    assert (d_out.cpu().numpy() == codes).all()
+    assert (d_st.cpu().numpy() == states).all()
+    # the device copy: the mixins of the entries without leaves as they were, the model's root in every
+    # accepted tree's entry, the zero root of a refused tree, _pad where the gate refuses, nothing else
+    after = d_ent.cpu().numpy().view(fa.POH_ENTRY_DTYPE)
+    has, okt = cnt > 0, (cnt > 0) & (tcodes == 0)
+    assert (after["mixin"][~has] == ent["mixin"][~has]).all()
+    assert (after["mixin"][okt] == roots[okt]).all() and roots[okt].any(axis=1).all()
+    assert not after["mixin"][has & ~okt].any()
+    assert (after["_pad"] == gated).all()
+    for f in ("start", "expect", "n", "flags"):
+        assert (after[f] == ent[f]).all(), f
+
+
 def test_timeout_then_recovery():
     """a packed entries call that gives up waiting writes nothing, and the
     next one waits the abandoned launches out before it uses the scratch"""
