@@ -55,6 +55,11 @@ POH_CHUNK_DEFAULT = 16384
 BMTREE_LEAF_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4")])
 BMTREE_LEAVES_ARE_NODES = 1   # FD_BMTREE_GPU_LEAVES_ARE_NODES
 BMTREE_LEAF_SZ_MAX = 65535    # FD_BMTREE_GPU_LEAF_SZ_MAX
+# fd_bmtree_gpu_proof_t: a leaf, its inclusion proof and where the walk should end, all offsets into one blob
+BMTREE_PROOF_DTYPE = np.dtype([("leaf_off", "<u4"), ("leaf_sz", "<u4"), ("proof_off", "<u4"), ("idx", "<u4"), ("leaf_cnt", "<u4"),
+                               ("depth", "<u4"), ("expect_off", "<u4"), ("flags", "<u4")])
+BMTREE_PROOF_EXPECT = 1       # FD_BMTREE_GPU_PROOF_EXPECT
+BMTREE_ERR_PROOF = -1         # FD_BMTREE_ERR_PROOF: the walk does not reach the expected root
 
 
 class Stages:
@@ -355,6 +360,18 @@ def lib() -> ctypes.CDLL:
         L.fd_bmtree_gpu_roots_packed.restype = ip
         L.fd_bmtree_gpu_roots_dev.argtypes = [vp, u, u, ul, vp, ul, vp, vp, ul, ul, vp, ul, vp, vp, vp]
         L.fd_bmtree_gpu_roots_dev.restype = ip
+        L.fd_bmtree_proofs_batch.argtypes = [u, u, ul, vp, vp, vp, ul, ul, vp, vp, vp, ul, ip]
+        L.fd_bmtree_proofs_batch.restype = ip
+        L.fd_bmtree_gpu_proofs_packed.argtypes = [vp, u, u, ul, vp, vp, vp, ul, ul, vp, vp, vp, ul]
+        L.fd_bmtree_gpu_proofs_packed.restype = ip
+        L.fd_bmtree_gpu_proofs_dev.argtypes = [vp, u, u, ul, vp, ul, vp, vp, ul, ul, vp, ul, vp, ul, vp, vp, vp]
+        L.fd_bmtree_gpu_proofs_dev.restype = ip
+        L.fd_bmtree_from_proofs_batch.argtypes = [u, u, ul, vp, vp, ul, ul, vp, vp, ip]
+        L.fd_bmtree_from_proofs_batch.restype = ip
+        L.fd_bmtree_gpu_from_proofs_packed.argtypes = [vp, u, u, ul, vp, vp, ul, ul, vp, vp]
+        L.fd_bmtree_gpu_from_proofs_packed.restype = ip
+        L.fd_bmtree_gpu_from_proofs_dev.argtypes = [vp, u, u, ul, vp, vp, ul, ul, vp, ul, vp, vp]
+        L.fd_bmtree_gpu_from_proofs_dev.restype = ip
         L.fd_bmtree_gpu_work_sz.argtypes = [ul, ul]
         L.fd_bmtree_gpu_work_sz.restype = ul
         L.fd_bmtree_gpu_merge_passes.argtypes = [u, ul, vp]
@@ -891,6 +908,60 @@ class Engine:
         if err:
             raise EngineError(f"bmtree_roots_dev: {strerror(err)}: {last_error()}")
 
+    def bmtree_proofs(self, width: int, leaf_cnt: np.ndarray, leaves: np.ndarray, blob: np.ndarray, leaf_max: int, flags: int = 0,
+                      proofs: np.ndarray = None):
+        """fd_bmtree_gpu_proofs_packed: bmtree_roots, and every leaf's
+        inclusion proof.  proofs: a C-contiguous (n_leaves, stride) uint8
+        array that receives leaf k's proof in row k, every other byte left
+        as it is (default: zeros of the smallest stride).  Returns (roots,
+        codes, proofs)."""
+        leaf_cnt, leaves, blob = _bmtree_inputs(leaf_cnt, leaves, blob)
+        n = len(leaf_cnt)
+        proofs = _bmtree_proof_rows(width, len(leaves), leaf_max, proofs)
+        roots = np.empty((n, 32), dtype=np.uint8)
+        codes = np.empty(n, dtype=np.int32)
+        err = lib().fd_bmtree_gpu_proofs_packed(self._h, width, flags, n, _p(leaf_cnt), _p(leaves), _p(blob), blob.nbytes, leaf_max,
+                                                _p(roots), _p(codes), _p(proofs), proofs.shape[1])
+        if err:
+            raise EngineError(f"bmtree_proofs: {strerror(err)}: {last_error()}")
+        return roots, codes, proofs
+
+    def bmtree_proofs_dev(self, width: int, n_trees: int, d_first: int, n_leaves: int, d_leaves: int, d_blob: int, blob_sz: int,
+                          leaf_max: int, d_roots: int, root_stride: int, d_proofs: int, proof_stride: int, d_codes: int, d_work: int,
+                          stream: int = 0, flags: int = 0) -> None:
+        """fd_bmtree_gpu_proofs_dev: bmtree_roots_dev, and leaf k's proof to
+        d_proofs + k proof_stride; queues the launches and returns."""
+        err = lib().fd_bmtree_gpu_proofs_dev(self._h, width, flags, n_trees, d_first or None, n_leaves, d_leaves or None,
+                                             d_blob or None, blob_sz, leaf_max, d_roots or None, root_stride, d_proofs or None,
+                                             proof_stride, d_codes or None, d_work or None, stream or None)
+        if err:
+            raise EngineError(f"bmtree_proofs_dev: {strerror(err)}: {last_error()}")
+
+    def bmtree_from_proofs(self, width: int, proofs: np.ndarray, blob: np.ndarray, depth_max: int, flags: int = 0):
+        """fd_bmtree_gpu_from_proofs_packed: the root every leaf and proof
+        (BMTREE_PROOF_DTYPE descriptors into blob) lead to as an (n, 32)
+        array, and its code (0, BMTREE_ERR_PROOF, or ERR_ARG for a refused
+        descriptor, whose root is zero)."""
+        proofs = np.ascontiguousarray(proofs, dtype=BMTREE_PROOF_DTYPE)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        n = len(proofs)
+        roots = np.empty((n, 32), dtype=np.uint8)
+        codes = np.empty(n, dtype=np.int32)
+        err = lib().fd_bmtree_gpu_from_proofs_packed(self._h, width, flags, n, _p(proofs), _p(blob), blob.nbytes, depth_max,
+                                                     _p(roots), _p(codes))
+        if err:
+            raise EngineError(f"bmtree_from_proofs: {strerror(err)}: {last_error()}")
+        return roots, codes
+
+    def bmtree_from_proofs_dev(self, width: int, n: int, d_proofs: int, d_blob: int, blob_sz: int, depth_max: int, d_roots: int,
+                               root_stride: int, d_codes: int, stream: int = 0, flags: int = 0) -> None:
+        """fd_bmtree_gpu_from_proofs_dev: device-resident (raw device
+        pointers); queues one launch and returns."""
+        err = lib().fd_bmtree_gpu_from_proofs_dev(self._h, width, flags, n, d_proofs or None, d_blob or None, blob_sz, depth_max,
+                                                  d_roots or None, root_stride, d_codes or None, stream or None)
+        if err:
+            raise EngineError(f"bmtree_from_proofs_dev: {strerror(err)}: {last_error()}")
+
     def sha512(self, msgs, is384: bool = False) -> list:
         """SHA-512 (SHA-384) digests of byte strings on the device."""
         n = len(msgs)
@@ -1264,6 +1335,47 @@ def bmtree_roots_batch(width: int, leaf_cnt, leaves, blob, leaf_max: int, flags:
                                       nthreads)
     if err:
         raise EngineError(f"bmtree_roots_batch: {strerror(err)}")
+    return roots, codes
+
+
+def bmtree_proof_stride(width: int, n_leaves: int, leaf_max: int) -> int:
+    """the smallest proof_stride of an emit call: width * ceil_log2(min(leaf_max, n_leaves))"""
+    m = min(int(leaf_max), int(n_leaves))
+    return width * (m - 1).bit_length() if m > 1 else 0
+
+
+def _bmtree_proof_rows(width: int, n_leaves: int, leaf_max: int, proofs):
+    if proofs is None:
+        return np.zeros((n_leaves, max(bmtree_proof_stride(width, n_leaves, leaf_max), 4)), dtype=np.uint8)
+    if proofs.dtype != np.uint8 or proofs.ndim != 2 or len(proofs) != n_leaves or not proofs.flags.c_contiguous:
+        raise ValueError("bmtree: proofs is a C-contiguous (n_leaves, stride) uint8 array")
+    return proofs
+
+
+def bmtree_proofs_batch(width: int, leaf_cnt, leaves, blob, leaf_max: int, flags: int = 0, nthreads: int = 8, proofs=None):
+    """fd_bmtree_proofs_batch: Engine.bmtree_proofs's semantics on host threads"""
+    leaf_cnt, leaves, blob = _bmtree_inputs(leaf_cnt, leaves, blob)
+    n = len(leaf_cnt)
+    proofs = _bmtree_proof_rows(width, len(leaves), leaf_max, proofs)
+    roots = np.empty((n, 32), dtype=np.uint8)
+    codes = np.empty(n, dtype=np.int32)
+    err = lib().fd_bmtree_proofs_batch(width, flags, n, _p(leaf_cnt), _p(leaves), _p(blob), blob.nbytes, leaf_max, _p(roots), _p(codes),
+                                       _p(proofs), proofs.shape[1], nthreads)
+    if err:
+        raise EngineError(f"bmtree_proofs_batch: {strerror(err)}")
+    return roots, codes, proofs
+
+
+def bmtree_from_proofs_batch(width: int, proofs, blob, depth_max: int, flags: int = 0, nthreads: int = 8):
+    """fd_bmtree_from_proofs_batch: Engine.bmtree_from_proofs's semantics on host threads"""
+    proofs = np.ascontiguousarray(proofs, dtype=BMTREE_PROOF_DTYPE)
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n = len(proofs)
+    roots = np.empty((n, 32), dtype=np.uint8)
+    codes = np.empty(n, dtype=np.int32)
+    err = lib().fd_bmtree_from_proofs_batch(width, flags, n, _p(proofs), _p(blob), blob.nbytes, depth_max, _p(roots), _p(codes), nthreads)
+    if err:
+        raise EngineError(f"bmtree_from_proofs_batch: {strerror(err)}")
     return roots, codes
 
 

@@ -122,4 +122,60 @@ FD_BMTREE_FN void fd_bmtree_leaf( uint32_t s[8], uint8_t const * p, uint32_t sz 
   fd_poh_compress( s, w );
 }
 
+/* Inclusion proofs (include/fd_bmtree_gpu.h).  A tree of c leaves has
+   depth ceil( log2( c ) ) and ceil( c / 2^l ) nodes in layer l; the proof
+   of leaf i holds, for each layer l below the root, the sibling ( i >> l ) ^ 1
+   of the node on its path, or that node itself where the layer ends before
+   the sibling (the node that is merged with itself). */
+
+/* ceil( log2( n ) ), 0 for n <= 1 */
+FD_BMTREE_FN uint32_t fd_bmtree_depth( uint32_t n ) {
+  uint32_t l = 0U;
+  while( l < 32U && ( (uint64_t)1 << l ) < (uint64_t)n ) l++;
+  return l;
+}
+
+/* the nodes of layer l <= 32 of a tree of c leaves */
+FD_BMTREE_FN uint32_t fd_bmtree_layer_cnt( uint32_t c, uint32_t l ) {
+  return (uint32_t)( ( (uint64_t)c + ( (uint64_t)1 << l ) - 1UL ) >> l );
+}
+
+/* node j of a layer of cl nodes has no sibling */
+FD_BMTREE_FN int fd_bmtree_no_sibling( uint32_t j, uint32_t cl ) { return ( j ^ 1U ) >= cl; }
+
+/* the node of a layer of cl nodes that the proof of a leaf below node j holds */
+FD_BMTREE_FN uint32_t fd_bmtree_proof_idx( uint32_t j, uint32_t cl ) { return fd_bmtree_no_sibling( j, cl ) ? j : ( j ^ 1U ); }
+
+/* One step of the walk at width W: node <- merge( p, node ) where the node
+   is a right child, merge( node, p ) where it is a left one, and
+   merge( node, node ) where it has no sibling (p is not read). */
+FD_BMTREE_FN void fd_bmtree_walk_step( uint32_t W, uint32_t node[8], uint32_t const * p, uint32_t right, int alone ) {
+  uint32_t a[8], b[8], s[8];
+  int words = W == 32U ? 8 : 5;
+  for( int k=0; k<words; k++ ) {
+    uint32_t sib = alone ? node[k] : p[k];
+    a[k] = right ? sib : node[k];
+    b[k] = right ? node[k] : sib;
+  }
+  if( W == 32U ) fd_bmtree_merge32( s, a, b ); else fd_bmtree_merge20( s, a, b );
+  for( int k=0; k<words; k++ ) node[k] = s[k];
+}
+
+/* One proof descriptor against the header's refusal rules: nonzero where it
+   may be walked.  nodes: the leaf is a ready node; sz_max the leaf size
+   limit; expect: the descriptor's flags ask for the comparison. */
+FD_BMTREE_FN int fd_bmtree_proof_ok( uint32_t W, int nodes, uint64_t blob_sz, uint32_t depth_max, uint32_t sz_max,
+                                     uint32_t leaf_off, uint32_t leaf_sz, uint32_t proof_off, uint32_t idx, uint32_t leaf_cnt,
+                                     uint32_t depth, uint32_t expect_off, uint32_t flags ) {
+  uint64_t lim = blob_sz < 0xffffffffUL ? blob_sz : 0xffffffffUL;
+  if( flags & ~1U ) return 0;
+  if( depth > depth_max || depth > 32U ) return 0;
+  if( (uint64_t)leaf_off + (uint64_t)leaf_sz > lim ) return 0;
+  if( leaf_sz > sz_max || ( nodes && leaf_sz != W ) ) return 0;
+  if( (uint64_t)proof_off + (uint64_t)depth * (uint64_t)W > lim ) return 0;
+  if( ( flags & 1U ) && (uint64_t)expect_off + (uint64_t)W > lim ) return 0;
+  if( !leaf_cnt ) return depth >= 32U || !( idx >> depth );
+  return idx < leaf_cnt && depth == fd_bmtree_depth( leaf_cnt );
+}
+
 #endif /* HEADER_fd_bmtree_core_h */

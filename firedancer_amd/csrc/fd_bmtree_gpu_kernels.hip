@@ -21,7 +21,13 @@
 
    Refusals are decided before anything is hashed: fd_k_bmtree_check flags
    the trees of bad leaf descriptors (one lane per leaf), the set-up kernels
-   add the count rules, and a refused tree has no node in any layer. */
+   add the count rules, and a refused tree has no node in any layer.
+
+   Inclusion proofs.  The emit calls add fd_k_bmtree_proof_gather before
+   each merge launch: the layers ping-pong between two buffers, so layer l
+   is there only between merge launch l-1 and merge launch l+1, and the
+   stream order is leaf, gather(0), merge(0), gather(1), merge(1), ...
+   fd_k_bmtree_from_proof walks one proof per lane in one launch. */
 
 #include "fd_bmtree_core.h"
 #include "fd_bmtree_gpu_private.h"
@@ -214,6 +220,101 @@ fd_k_bmtree_merge20( fd_bmtree_plan_t p, uint32_t const * so, uint32_t const * d
   fd_bmtree_merge_body<20u>( p, so, dn, src, src_cap, dst, dst_cap );
 }
 
+/* gather launch l, before merge launch l: one lane per leaf writes node l
+   of its proof, the sibling in layer l (src, offsets so; l = 0: the leaves,
+   first) of the node on its path, or that node where it has no sibling, to
+   its row at l W.  Dword stores only: rows and W are multiples of 4.  The
+   lanes of refused trees and of trees of depth <= l leave. */
+extern "C" __global__ void __launch_bounds__(256)
+fd_k_bmtree_proof_gather( fd_bmtree_plan_t p, uint32_t l, uint32_t const * so, uint32_t const * src, uint32_t src_cap ) {
+  uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if( i >= p.N ) return;
+  uint32_t t = fd_bmtree_find( p.first, p.T, i );
+  if( p.bad[t] ) return;
+  uint32_t f0 = p.first[t], f1 = p.first[t+1u];
+  if( i < f0 || i >= f1 ) return;                 /* not with offsets as documented */
+  uint32_t cl = fd_bmtree_layer_cnt( f1 - f0, l );
+  if( cl <= 1u ) return;                          /* l >= D: the root is no proof node */
+  uint32_t base = l ? so[t] : f0;
+  uint64_t k = (uint64_t)base + fd_bmtree_proof_idx( ( i - f0 ) >> l, cl );
+  if( k >= src_cap ) return;
+  uint4 const * pn = (uint4 const *)( src + 8UL*k );
+  uint4 n0 = pn[0], n1 = pn[1];
+  uint32_t * row = (uint32_t *)( p.proofs + (uint64_t)i * p.proof_stride + (uint64_t)l * p.width );
+  row[0] = __builtin_bswap32( n0.x ); row[1] = __builtin_bswap32( n0.y ); row[2] = __builtin_bswap32( n0.z );
+  row[3] = __builtin_bswap32( n0.w ); row[4] = __builtin_bswap32( n1.x );
+  if( p.width == 32u ) { row[5] = __builtin_bswap32( n1.y ); row[6] = __builtin_bswap32( n1.z ); row[7] = __builtin_bswap32( n1.w ); }
+}
+
+/* n big-endian words from 4 n bytes at any alignment, word loads where the
+   address allows them */
+static __device__ __forceinline__ void fd_bmtree_load_any( uint32_t * d, uint8_t const * q, int words ) {
+  if( !( (uintptr_t)q & 3UL ) ) {
+    uint32_t const * q4 = (uint32_t const *)q;
+    for( int k=0; k<words; k++ ) d[k] = __builtin_bswap32( q4[k] );
+  } else {
+    fd_bmtree_load( d, q, words );
+  }
+}
+
+/* One lane per proof: the descriptor's check (a refused lane writes its
+   code and its zero root and leaves), the leaf node as in fd_k_bmtree_leaf,
+   the walk to the lane's depth, the comparison, the root and the code.
+   roots may lie inside blob (a part no descriptor reads), so neither is
+   __restrict__. */
+template< uint32_t W > static __device__ __forceinline__ void
+fd_bmtree_walk_body( fd_bmtree_walk_plan_t const & p ) {
+  uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if( i >= p.n ) return;
+  fd_bmtree_gpu_proof_t d = p.desc[i];
+  uint32_t * r = (uint32_t *)( p.roots + (uint64_t)i * p.root_stride );
+  int nodes = !!( p.flags & FD_BMTREE_GPU_LEAVES_ARE_NODES );
+  if( !fd_bmtree_proof_ok( W, nodes, p.blob_sz, p.depth_max, FD_BMTREE_GPU_LEAF_SZ_MAX, d.leaf_off, d.leaf_sz, d.proof_off, d.idx,
+                           d.leaf_cnt, d.depth, d.expect_off, d.flags ) ) {
+#pragma unroll
+    for( int j=0; j<8; j++ ) r[j] = 0u;
+    p.codes[i] = FD_ED25519_ERR_ARG;
+    return;
+  }
+  constexpr int words = W == 32u ? 8 : 5;
+  uint8_t const * src = p.blob + d.leaf_off;
+  uint32_t s[8];
+  if( nodes ) {
+    fd_bmtree_load_any( s, src, words );
+  } else if( __all( d.leaf_sz == 64u ) ) {
+    uint32_t m[16];
+    fd_bmtree_load_any( m, src, 16 );
+    fd_bmtree_leaf64( s, m );
+  } else {
+    fd_bmtree_leaf( s, src, d.leaf_sz );
+  }
+  uint8_t const * q = p.blob + d.proof_off;
+#pragma nounroll
+  for( uint32_t l=0u; l<d.depth; l++, q+=W ) {
+    int alone = d.leaf_cnt && fd_bmtree_no_sibling( d.idx >> l, fd_bmtree_layer_cnt( d.leaf_cnt, l ) );
+    uint32_t pn[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+    if( !alone ) fd_bmtree_load_any( pn, q, words );
+    fd_bmtree_walk_step( W, s, pn, ( d.idx >> l ) & 1u, alone );
+  }
+  int32_t code = 0;
+  if( d.flags & FD_BMTREE_GPU_PROOF_EXPECT ) {
+    uint32_t e[8];
+    fd_bmtree_load_any( e, p.blob + d.expect_off, words );
+    uint32_t diff = 0u;
+#pragma unroll
+    for( int k=0; k<words; k++ ) diff |= e[k] ^ s[k];
+    if( diff ) code = FD_BMTREE_ERR_PROOF;
+  }
+#pragma unroll
+  for( int j=0; j<8; j++ ) r[j] = j < words ? __builtin_bswap32( s[j] ) : 0u;
+  p.codes[i] = code;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+fd_k_bmtree_from_proof( fd_bmtree_walk_plan_t p ) {
+  if( p.width == 32u ) fd_bmtree_walk_body<32u>( p ); else fd_bmtree_walk_body<20u>( p );
+}
+
 /* one lane per Proof-of-History entry (fd_bmtree_gpu_private.h) */
 extern "C" __global__ void __launch_bounds__(256)
 fd_k_bmtree_poh_gate( uint32_t n, uint32_t const * __restrict__ first, int32_t const * __restrict__ tree_codes,
@@ -242,10 +343,17 @@ extern "C" hipError_t fd_bmtree_gpu_launch( fd_bmtree_plan_t const * pp, uint32_
     uint32_t * src = ( l & 1u ) ? p.node_b : p.node_a;  uint32_t src_cap = ( l & 1u ) ? p.cap_b : p.cap_a;
     uint32_t * dst = ( l & 1u ) ? p.node_a : p.node_b;  uint32_t dst_cap = ( l & 1u ) ? p.cap_a : p.cap_b;
     uint32_t n = lanes[l] < dst_cap ? lanes[l] : dst_cap;
-    if( !n ) continue;
+    if( !n ) continue;                            /* no tree has two nodes in layer l: nothing to gather either */
+    if( p.proofs && p.N ) hipLaunchKernelGGL( fd_k_bmtree_proof_gather, dim3((p.N + 255u) / 256u), dim3(256), 0, stream, p, l, so, src, src_cap );
     if( p.width == 32u ) hipLaunchKernelGGL( fd_k_bmtree_merge32, dim3((n + 63u) / 64u), dim3(64), 0, stream, p, so, dn, src, src_cap, dst, dst_cap );
     else                 hipLaunchKernelGGL( fd_k_bmtree_merge20, dim3((n + 63u) / 64u), dim3(64), 0, stream, p, so, dn, src, src_cap, dst, dst_cap );
   }
+  return hipGetLastError();
+}
+
+extern "C" hipError_t fd_bmtree_gpu_walk_launch( fd_bmtree_walk_plan_t const * pp, hipStream_t stream ) {
+  if( !pp->n ) return hipSuccess;
+  hipLaunchKernelGGL( fd_k_bmtree_from_proof, dim3((pp->n + 255u) / 256u), dim3(256), 0, stream, *pp );
   return hipGetLastError();
 }
 

@@ -41,7 +41,20 @@ typedef struct {
   uint32_t * part;             /* L rows of NB: the blocks' sums, then their exclusive prefix */
   uint32_t * node_a;  uint32_t cap_a;   /* capacities in nodes */
   uint32_t * node_b;  uint32_t cap_b;
+  uint8_t *  proofs;           /* the emit calls: leaf i's proof row at proofs + i proof_stride; else NULL */
+  uint64_t   proof_stride;
 } fd_bmtree_plan_t;
+
+/* One from-proofs call: one lane per descriptor, no work memory. */
+typedef struct {
+  uint32_t width, flags;
+  uint32_t n, blob_sz, depth_max;
+  fd_bmtree_gpu_proof_t const * desc;
+  uint8_t const *               blob;
+  uint8_t *  roots;
+  uint64_t   root_stride;
+  int32_t *  codes;
+} fd_bmtree_walk_plan_t;
 
 static inline uint32_t fd_bmtree_ceil_log2( unsigned long n ) {
   uint32_t l = 0U;
@@ -90,8 +103,14 @@ static inline void fd_bmtree_plan_make( fd_bmtree_plan_t * p, unsigned width, un
 
 /* Queues the whole call on stream: clear, check, the three offset kernels,
    the leaf kernel, and merge launch l = 0..L-1 over lanes[l] lanes (an
-   upper bound of layer l+1's node count; the lanes past the count leave). */
+   upper bound of layer l+1's node count; the lanes past the count leave).
+   With p->proofs, gather launch l (one lane per leaf) goes before merge
+   launch l: layer l is in its buffer only from merge launch l-1, which
+   writes it, to merge launch l+1, which overwrites it. */
 extern "C" hipError_t fd_bmtree_gpu_launch( fd_bmtree_plan_t const * p, uint32_t const * lanes, hipStream_t stream );
+
+/* the one launch of a from-proofs call */
+extern "C" hipError_t fd_bmtree_gpu_walk_launch( fd_bmtree_walk_plan_t const * p, hipStream_t stream );
 
 /* fd_poh_gpu.cpp: entry i with leaves (first[i+1] > first[i]) whose tree is
    refused (tree_codes[i] != 0) or which lacks FD_POH_GPU_MIXIN gets a

@@ -170,6 +170,171 @@ fd_bmtree_gpu_merge_passes( unsigned         width,
                             unsigned long    n_trees,
                             uint32_t const * leaf_cnt );
 
+/* Inclusion proofs.  The reference has the commit interface only, so the
+   proof format is this library's, pinned to the reference through the root
+   every proof walks to.  A tree of c leaves has depth D = ceil( log2( c ) )
+   (0 for c = 1); layer 0 is the leaf nodes and layer l+1 has
+   ceil( c_l / 2 ) nodes.
+
+     proof of leaf i: D nodes of W bytes, packed, level 0 first.  Node l is
+       the layer-l node ( i >> l ) ^ 1, or, where that index is >= c_l (the
+       node on the path has no right sibling and is merged with itself),
+       the node i >> l itself.
+     walk: node = leaf( data ) (or the ready node); for l = 0 .. depth-1,
+       p = proof[l], node = ( idx >> l ) & 1 ? merge( p, node )
+                                             : merge( node, p ).
+       The result is the derived root.
+     strict walk (leaf_cnt != 0): the walk of exactly that tree: depth ==
+       ceil( log2( leaf_cnt ) ), idx < leaf_cnt, and at a level where
+       ( idx >> l ) ^ 1 >= c_l the proof node is not read and the node is
+       merged with itself, so a prover cannot choose that sibling. */
+
+/* the walk does not reach the expected root */
+#define FD_BMTREE_ERR_PROOF (-1)
+
+/* Emit.  The roots calls, and every leaf's proof: leaf k of the call, in
+   descriptor order, gets the W D bytes of its proof (D of its tree) at
+   proofs + k proof_stride; nothing else in a row is touched and the rows
+   of a refused tree are not touched.  proof_stride is a multiple of 4 and
+   at least W ceil( log2( min( leaf_max, n_leaves ) ) ), the base is 4-byte
+   aligned and not NULL where there are leaves; otherwise
+   FD_ED25519_ERR_ARG.  Roots, codes and return values are the roots
+   calls'; the host version also returns FD_ED25519_ERR_ARG where its
+   per-thread layer buffers cannot be allocated. */
+int
+fd_bmtree_proofs_batch( unsigned                     width,
+                        unsigned                     flags,
+                        unsigned long                n_trees,
+                        uint32_t const *             leaf_cnt,
+                        fd_bmtree_gpu_leaf_t const * leaves,
+                        void const *                 blob,
+                        unsigned long                blob_sz,
+                        unsigned long                leaf_max,
+                        void *                       roots_out,
+                        int *                        codes_out,
+                        void *                       proofs_out,
+                        unsigned long                proof_stride,
+                        int                          nthreads );
+
+int
+fd_bmtree_gpu_proofs_packed( fd_ed25519_gpu_t *           gpu,
+                             unsigned                     width,
+                             unsigned                     flags,
+                             unsigned long                n_trees,
+                             uint32_t const *             leaf_cnt,
+                             fd_bmtree_gpu_leaf_t const * leaves,
+                             void const *                 blob,
+                             unsigned long                blob_sz,
+                             unsigned long                leaf_max,
+                             void *                       roots_out,
+                             int *                        codes_out,
+                             void *                       proofs_out,
+                             unsigned long                proof_stride );
+
+/* d_proofs = d_shreds + merkle_off with proof_stride the shred size drops
+   each proof into its shred's tail.  d_work is fd_bmtree_gpu_work_sz(
+   n_trees, n_leaves ) bytes as for the roots call: the layers are gathered
+   from between the merge launches (one gather launch before each), and
+   nothing is read back. */
+int
+fd_bmtree_gpu_proofs_dev( fd_ed25519_gpu_t *           gpu,
+                          unsigned                     width,
+                          unsigned                     flags,
+                          unsigned long                n_trees,
+                          uint32_t const *             d_first,
+                          unsigned long                n_leaves,
+                          fd_bmtree_gpu_leaf_t const * d_leaves,
+                          void const *                 d_blob,
+                          unsigned long                blob_sz,
+                          unsigned long                leaf_max,
+                          void *                       d_roots,
+                          unsigned long                root_stride,
+                          void *                       d_proofs,
+                          unsigned long                proof_stride,
+                          int *                        d_codes,
+                          void *                       d_work,
+                          void *                       stream );
+
+/* Verify: the root a leaf and its proof lead to.  Every offset is into the
+   call's blob. */
+typedef struct {
+  uint32_t leaf_off, leaf_sz;   /* the leaf's data, or with FD_BMTREE_GPU_LEAVES_ARE_NODES a ready node (leaf_sz == width) */
+  uint32_t proof_off;           /* depth nodes of width bytes, packed, any alignment */
+  uint32_t idx;                 /* the leaf's index in its tree */
+  uint32_t leaf_cnt;            /* 0: not known (plain walk); else strict walk */
+  uint32_t depth;
+  uint32_t expect_off;          /* read only with FD_BMTREE_GPU_PROOF_EXPECT */
+  uint32_t flags;               /* FD_BMTREE_GPU_PROOF_EXPECT; other bits refuse */
+} fd_bmtree_gpu_proof_t;
+
+/* compare the derived root with blob[expect_off, expect_off+W) */
+#define FD_BMTREE_GPU_PROOF_EXPECT (1U)
+
+/* Proof i's derived root goes to roots_out + 32 i (a W = 20 root is
+   followed by 12 zero bytes); codes_out[i] is 0, FD_BMTREE_ERR_PROOF (only
+   with FD_BMTREE_GPU_PROOF_EXPECT: the derived root, which is still
+   written, differs from the expected one) or FD_ED25519_ERR_ARG for a
+   refused descriptor, which is never hashed, of which nothing is
+   dereferenced and whose root is 32 zero bytes:
+     a leaf, proof (depth W bytes) or expect range past blob_sz or wrapping
+       32 bits,
+     leaf_sz > FD_BMTREE_GPU_LEAF_SZ_MAX, in node mode leaf_sz != width,
+     depth > depth_max (1..32; it bounds a lane's work as leaf_max does),
+     unknown flag bits,
+     leaf_cnt == 0: depth < 32 and idx >> depth != 0,
+     leaf_cnt != 0: idx >= leaf_cnt or depth != ceil( log2( leaf_cnt ) ).
+   A refused descriptor does not disturb its neighbours.  Returns 0 or
+   FD_ED25519_ERR_ARG (NULL array, width, unknown call flags, depth_max, n
+   past FD_BMTREE_GPU_LEAVES_MAX, thread count). */
+int
+fd_bmtree_from_proofs_batch( unsigned                      width,
+                             unsigned                      flags,
+                             unsigned long                 n,
+                             fd_bmtree_gpu_proof_t const * proofs,
+                             void const *                  blob,
+                             unsigned long                 blob_sz,
+                             unsigned long                 depth_max,
+                             void *                        roots_out,
+                             int *                         codes_out,
+                             int                           nthreads );
+
+/* The same on the device, synchronous, host buffers: call-level errors as
+   for fd_bmtree_gpu_roots_packed (blob_sz >= 2^32 is FD_ED25519_ERR_ARG; on
+   FD_ED25519_ERR_GPU nothing is written; no host fallback). */
+int
+fd_bmtree_gpu_from_proofs_packed( fd_ed25519_gpu_t *            gpu,
+                                  unsigned                      width,
+                                  unsigned                      flags,
+                                  unsigned long                 n,
+                                  fd_bmtree_gpu_proof_t const * proofs,
+                                  void const *                  blob,
+                                  unsigned long                 blob_sz,
+                                  unsigned long                 depth_max,
+                                  void *                        roots_out,
+                                  int *                         codes_out );
+
+/* Device-resident: one launch on `stream` (NULL: the engine's tree stream),
+   no work memory, no host synchronisation.  Root i goes to d_roots + i
+   root_stride under fd_bmtree_gpu_roots_dev's alignment rules; d_proofs is
+   4-byte aligned.  d_roots may point into a part of d_blob that no
+   descriptor reads: the roots are then messages in place for
+   fd_ed25519_gpu_verify_dev on the same stream (a stream of the caller's:
+   with NULL each of the two calls takes a stream of its own unit and they
+   are not ordered). */
+int
+fd_bmtree_gpu_from_proofs_dev( fd_ed25519_gpu_t *            gpu,
+                               unsigned                      width,
+                               unsigned                      flags,
+                               unsigned long                 n,
+                               fd_bmtree_gpu_proof_t const * d_proofs,
+                               void const *                  d_blob,
+                               unsigned long                 blob_sz,
+                               unsigned long                 depth_max,
+                               void *                        d_roots,
+                               unsigned long                 root_stride,
+                               int *                         d_codes,
+                               void *                        stream );
+
 #ifdef __cplusplus
 }
 #endif
