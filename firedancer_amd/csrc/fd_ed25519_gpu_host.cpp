@@ -112,25 +112,24 @@ static int fd_event_query( void * ev ) {
   return -1;
 }
 
-/* wait for a slot's completion event: 0 done, FD_ED25519_ERR_GPU on a
-   runtime failure or after timeout_ns (the batch may still complete; the
-   caller may poll again) */
-static int fd_event_wait( hipEvent_t ev, long timeout_ns ) {
-  int r = fd_wait_query( fd_event_query, (void *)ev, FD_POLL_SPIN_NS, timeout_ns );
-  if( r == 1 ) return 0;
-  if( r == 0 ) {
-    snprintf( fd_gpu_err, sizeof(fd_gpu_err), "wait: batch not complete after %ld ms", timeout_ns / 1000000L );
-    return FD_ED25519_ERR_GPU;
-  }
-  return FD_ED25519_ERR_GPU;
+/* a blocking wait on a batch's completion: what query returned (> 0), or
+   FD_ED25519_ERR_GPU on a runtime failure or after timeout_ns (the batch
+   may still complete; the caller may poll again).  who: names a side unit
+   in the text, or "" */
+static int fd_batch_wait( int (*query)( void * ), void * ctx, long timeout_ns, char const * who ) {
+  int r = fd_wait_query( query, ctx, FD_POLL_SPIN_NS, timeout_ns );
+  if( r == 0 ) snprintf( fd_gpu_err, sizeof(fd_gpu_err), "%s%swait: batch not complete after %ld ms", who, *who ? " " : "", timeout_ns / 1000000L );
+  return r > 0 ? r : FD_ED25519_ERR_GPU;
 }
 
-/* fd_event_wait for the side units, within the engine's timeout: the text names the unit */
+/* wait for a slot's completion event: 0 done, else FD_ED25519_ERR_GPU */
+static int fd_event_wait( hipEvent_t ev, long timeout_ns ) {
+  return fd_batch_wait( fd_event_query, (void *)ev, timeout_ns, "" ) > 0 ? 0 : FD_ED25519_ERR_GPU;
+}
+
+/* fd_event_wait for the side units, within the engine's timeout */
 int fd_ed25519_gpu_unit_wait( fd_ed25519_gpu_t * g, hipEvent_t ev, char const * who ) {
-  long to = fd_ed25519_gpu_timeout( g );
-  int r = fd_wait_query( fd_event_query, (void *)ev, FD_POLL_SPIN_NS, to );
-  if( r == 0 ) snprintf( fd_gpu_err, sizeof(fd_gpu_err), "%s wait: batch not complete after %ld ms", who, to / 1000000L );
-  return r == 1 ? 0 : FD_ED25519_ERR_GPU;
+  return fd_batch_wait( fd_event_query, (void *)ev, fd_ed25519_gpu_timeout( g ), who ) > 0 ? 0 : FD_ED25519_ERR_GPU;
 }
 
 /* Self-test of the bounded wait without a device (tests/test_abi.py): a
@@ -392,7 +391,7 @@ extern "C" fd_ed25519_gpu_t * fd_ed25519_gpu_new_ex( int device, unsigned long m
     HIPCHK( hipHostMalloc( (void **)&sl->h_desc, max_sigs * sizeof(fd_ed25519_gpu_desc_t), hipHostMallocMapped ) );
     if( hipHostGetDevicePointer( (void **)&sl->h_desc_dev, sl->h_desc, 0 ) != hipSuccess ) { (void)hipGetLastError(); sl->h_desc_dev = NULL; }
     /* codes of small batches are written by the kernels straight into
-       h_out (fine-grained, mapped: no D2H copy, fd_slot_enqueue_) */
+       h_out (fine-grained, mapped: no D2H copy, fd_ring_verify) */
     HIPCHK( hipHostMalloc( (void **)&sl->h_out,  max_sigs * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent ) );
     if( hipHostGetDevicePointer( (void **)&sl->h_out_dev, sl->h_out, 0 ) != hipSuccess ) { (void)hipGetLastError(); sl->h_out_dev = NULL; }
     HIPCHK( hipMalloc( (void **)&sl->d_blob, blob_cap ) );
@@ -682,12 +681,24 @@ static void fd_reclaim_orphans( fd_ed25519_gpu_t * g ) {
   }
 }
 
+/* the slot holding ticket (never 0) / the slot whose pinned blob buffer is
+   blob, or NULL.  Caller holds g->lock. */
+static fd_ed25519_gpu_slot * fd_slot_by_ticket( fd_ed25519_gpu_t * g, unsigned long ticket ) {
+  for( int s=0; s<g->depth; s++ ) if( g->slot[s].ticket == ticket ) return &g->slot[s];
+  return NULL;
+}
+static fd_ed25519_gpu_slot * fd_slot_by_blob( fd_ed25519_gpu_t * g, void const * blob ) {
+  for( int s=0; s<g->depth; s++ ) if( g->slot[s].h_blob == blob ) return &g->slot[s];
+  return NULL;
+}
+
 /* Give up on a submitted ticket nobody will poll again (its blocking poll
    timed out): the slot is reclaimed by fd_reclaim_orphans once the batch
    drains, instead of staying taken for the engine's lifetime. */
 static void fd_abandon_ticket( fd_ed25519_gpu_t * g, unsigned long ticket ) {
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  for( int s=0; s<g->depth; s++ ) if( g->slot[s].ticket == ticket ) g->slot[s].orphan = 1;
+  fd_ed25519_gpu_slot * sl = fd_slot_by_ticket( g, ticket );
+  if( sl ) sl->orphan = 1;
 }
 
 /* No slot is free, but one whose codes a poll took early is only retiring
@@ -734,14 +745,16 @@ extern "C" int fd_ed25519_gpu_stage( fd_ed25519_gpu_t * g, void ** blob, fd_ed25
 extern "C" void fd_ed25519_gpu_unstage( fd_ed25519_gpu_t * g, void const * blob ) {
   if( !g ) return;
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  for( int s=0; s<g->depth; s++ ) if( g->slot[s].h_blob == blob ) g->slot[s].staged = 0;
+  fd_ed25519_gpu_slot * sl = fd_slot_by_blob( g, blob );
+  if( sl ) sl->staged = 0;
 }
 
 /* a free slot: the staged one owning `blob` if any, else any unstaged one
    (slots orphaned by a timed-out synchronous call come back once done) */
 static fd_ed25519_gpu_slot * fd_free_slot_( fd_ed25519_gpu_t * g, void const * blob ) {
   fd_reclaim_orphans( g );
-  for( int s=0; s<g->depth; s++ ) if( !g->slot[s].ticket && g->slot[s].h_blob == blob ) return &g->slot[s];
+  fd_ed25519_gpu_slot * own = fd_slot_by_blob( g, blob );
+  if( own && !own->ticket ) return own;
   if( g->groups > 1 ) {
     /* slot s runs on CU group s mod groups: of the free slots, take one on
        the group with the fewest batches in flight, so a ring kept below
@@ -770,13 +783,26 @@ static fd_ed25519_gpu_slot * fd_free_slot( fd_ed25519_gpu_t * g, void const * bl
   return sl;
 }
 
-/* ---- The slot lifecycle of a synchronous call ----------------------------
+/* ---- The two slot lifecycles ----------------------------------------------
 
-   take -> stage -> enqueue -> settle, all under g->lock.  The call takes a
-   free slot, stages its input in the slot's pinned blob, queues its own
-   HIP work and the slot's done event on the slot's stream, and hands the
-   outcome to fd_slot_settle, the one way out: no path returns with work
-   queued on a slot that is neither waited for nor orphaned. */
+   A synchronous call: take -> stage -> enqueue -> settle, all under
+   g->lock.  The call takes a free slot, stages its input in the slot's
+   pinned blob, queues its own HIP work and the slot's done event on the
+   slot's stream, and hands the outcome to fd_slot_settle, the one way out:
+   no path returns with work queued on a slot that is neither waited for
+   nor orphaned.
+
+   A ring batch of either kind (fd_ring_submit, fd_ring_poll): take ->
+   enqueue -> ticket under one hold of g->lock (a failed enqueue is settled
+   as above; the stage submitted from is released either way), then polls,
+   which wait outside the lock.  A poll that times out or is refused ends
+   nothing: the ticket stays valid.  One that collects ends in
+     free    the ticket is cleared;
+     retire  a small batch's codes were taken as they landed: the slot keeps
+             its ticket until fd_reclaim_orphans sees its done event;
+     keep    either, and the pinned buffers stay the caller's until unstaged;
+     orphan  (fd_abandon_ticket, for a caller that gives up) as retire, and
+             a stage goes with the slot. */
 
 /* Take: the device and a free slot (the staged one owning blob, if any).
    0, the fd_gpu_fail code, or FD_ED25519_ERR_ARG when every slot is in
@@ -788,14 +814,17 @@ static int fd_slot_take( fd_ed25519_gpu_t * g, void const * blob, fd_ed25519_gpu
 }
 
 /* Stage: the blob into the slot's pinned buffer (unless it is that
-   buffer), zeros up to the 16-aligned offset behind its pad, and the
-   descriptors (or whatever travels in their place) there, so the batch is
-   one H2D copy.  Returns that offset. */
-static unsigned long fd_slot_stage( fd_ed25519_gpu_slot * sl, void const * blob, unsigned long blob_sz, void const * tail, unsigned long tail_sz ) {
-  unsigned long doff = fd_desc_off( blob_sz );
-  if( sl->h_blob != blob ) memcpy( sl->h_blob, blob, blob_sz );
+   buffer), a second piece behind it (blob2_sz 0: none), zeros up to the
+   16-aligned offset behind its pad, and the descriptors (or whatever
+   travels in their place; NULL: the caller writes it there) at that
+   offset, so the batch is one H2D copy.  Returns that offset. */
+static unsigned long fd_slot_stage( fd_ed25519_gpu_slot * sl, void const * blob, unsigned long sz0, void const * blob2, unsigned long blob2_sz,
+                                    void const * tail, unsigned long tail_sz ) {
+  unsigned long blob_sz = sz0 + blob2_sz, doff = fd_desc_off( blob_sz );
+  if( sl->h_blob != blob && sz0 ) memcpy( sl->h_blob, blob, sz0 );
+  if( blob2_sz ) memcpy( sl->h_blob + sz0, blob2, blob2_sz );
   memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
-  memcpy( sl->h_blob + doff, tail, tail_sz );
+  if( tail ) memcpy( sl->h_blob + doff, tail, tail_sz );
   return doff;
 }
 
@@ -999,95 +1028,117 @@ extern "C" int fd_ed25519_gpu_verify_dev_timed( fd_ed25519_gpu_t * g, unsigned l
 
 extern "C" int fd_ed25519_gpu_kernel_cnt( void ) { return FD_ED25519_GPU_KERNEL_CNT; }
 
-/* Stage a batch into a slot's pinned buffers and enqueue copy-in,
-   kernels, copy-out on the slot's stream.  Descriptors are copied as
-   given: the device checks each against blob_sz and reports an
-   out-of-bounds one as FD_ED25519_ERR_ARG (fd_k_prep). */
-static int fd_ring_busy( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot const * sl );
+/* The stream of a ring batch of n signatures: the slot's CU group only while
+   another ring batch is in flight (a lone batch runs faster spread over
+   the whole device: depth-1 p50 0.755 ms there vs 0.80 ms on a third of
+   the CUs) */
+static hipStream_t fd_ring_stream( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n ) {
+  int busy = 0;
+  for( int s=0; s<g->depth && !busy; s++ )
+    busy = &g->slot[s] != sl && g->slot[s].ticket && hipEventQuery( g->slot[s].done ) == hipErrorNotReady;
+  int others = sl->mstream && n <= g->mask_max && (g->group_always || busy);
+  return others ? sl->mstream : sl->stream;
+}
+
+/* Place: decide how the batch travels, and stage what must be staged.
+   The batch's bytes are blob[0, sz0) followed by blob2[0, blob2_sz) (a
+   second piece: an in-place batch that continues past the caller's ring
+   wrap); descriptors index the concatenation.  tail: what travels behind
+   the blob, at doff in the device's layout: the caller's descriptors
+   (copied as given: the device checks each against blob_sz and reports an
+   out-of-bounds one as FD_ED25519_ERR_ARG, fd_k_prep), or NULL where the
+   caller builds it at the returned .tail (a transaction batch's entries and
+   claim prefix) -- it lies nowhere yet, so it is never direct or packed. */
+struct fd_ring_src {
+  void const *  blob, * blob2;
+  unsigned long sz0, blob2_sz, doff, tail_sz;
+  uint8_t *     tail;
+  int           direct, packed, zc;
+};
+static fd_ring_src fd_ring_place( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, void const * blob, unsigned long sz0,
+                                  void const * blob2, unsigned long blob2_sz, void const * tail, unsigned long tail_sz ) {
+  fd_ring_src p = { blob, blob2, sz0, blob2_sz, fd_desc_off( sz0 + blob2_sz ), tail_sz, (uint8_t *)sl->h_desc, 0, 0, 0 };
+  /* a blob in a registered region is DMA'd from where it lies (no host
+     copy; the tail goes separately from the slot's pinned desc buffer);
+     anything else (the slot's own staged h_blob as it lies) is staged into
+     the slot's pinned buffer with the tail packed after it (one copy) */
+  p.direct = sl->h_blob != blob && sz0 && fd_registered( g, blob, sz0 ) && ( !blob2_sz || fd_registered( g, blob2, blob2_sz ) );
+  /* descriptors in a registered region too go from where they lie (a
+     verify tile building batches in its own registered buffers) */
+  int const tdirect = p.direct && tail && fd_registered( g, tail, tail_sz );
+  /* ... and packed right after the blob in the device's layout: one copy */
+  p.packed = tdirect && !blob2_sz && (uint8_t const *)tail == (uint8_t const *)blob + p.doff && fd_registered( g, blob, p.doff + tail_sz );
+  /* a registered span whose tail lies elsewhere (the feeder rebases
+     descriptors; an in-place tile keeps them apart from the frags; a
+     transaction batch's 12 bytes per transaction are built here): the
+     kernels read it over PCIe from the slot's mapped descriptor buffer
+     instead of a second H2D copy per batch (closed loop +1-2.5 %, p50
+     -0.01 ms, profiles/r06_zc_desc_ab_*.jsonl) */
+  p.zc = p.direct && !p.packed && sl->h_desc_dev;
+  if( !p.direct ) p.tail = sl->h_blob + fd_slot_stage( sl, blob, sz0, blob2, blob2_sz, tail, tail_sz );
+  else if( tdirect && !p.zc ) p.tail = (uint8_t *)tail;
+  else if( tail ) memcpy( p.tail, tail, tail_sz );
+  return p;
+}
+
+/* Copy in, on st: one copy of the staged batch or of the caller's packed
+   region; else the blob, piece 2 and (unless the kernels read it in place)
+   the tail.  Returns the tail as the kernels address it, NULL on failure. */
+static void const * fd_ring_h2d( fd_ed25519_gpu_slot * sl, fd_ring_src const & p, hipStream_t st ) {
+  hipError_t e;
+  if( p.packed || !p.direct ) e = hipMemcpyAsync( sl->d_blob, p.packed ? p.blob : sl->h_blob, p.doff + p.tail_sz, hipMemcpyHostToDevice, st );
+  else {
+    e = hipMemcpyAsync( sl->d_blob, p.blob, p.sz0, hipMemcpyHostToDevice, st );
+    if( e == hipSuccess && p.blob2_sz ) e = hipMemcpyAsync( sl->d_blob + p.sz0, p.blob2, p.blob2_sz, hipMemcpyHostToDevice, st );
+    if( e == hipSuccess && !p.zc )      e = hipMemcpyAsync( sl->d_blob + p.doff, p.tail, p.tail_sz, hipMemcpyHostToDevice, st );
+  }
+  if( e != hipSuccess ) { fd_gpu_fail_q( p.direct ? "H2D batch (registered)" : "H2D batch", e ); return NULL; }
+  return p.zc ? (void const *)sl->h_desc_dev : (void const *)( sl->d_blob + p.doff );
+}
+
+/* Verify: the launch on the slot's work area.  Up to out_direct_max
+   signatures the DSM writes its codes into the slot's pinned h_out itself:
+   no D2H copy (a blit kernel and its gap, ~5 us of every small batch's
+   round trip); they are visible to the host once the slot's done event
+   completes -- or, with early set, to a poll as they land over
+   FD_CODE_PENDING (fd_codes_query).  Returns where they go, or NULL. */
+static int32_t * fd_ring_verify( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n, unsigned long blob_sz,
+                                 void const * d_desc, hipStream_t st, int early ) {
+  int odirect = sl->h_out_dev && n <= g->out_direct_max;
+  int32_t * codes = odirect ? sl->h_out_dev : sl->d_out;
+  sl->early = early && odirect && n <= g->early_max;
+  if( sl->early ) for( unsigned long i=0; i<n; i++ ) sl->h_out[i] = FD_CODE_PENDING;
+  hipError_t e = fd_ed25519_gpu_launch( n, sl->d_blob, blob_sz, (fd_ed25519_gpu_desc_t const *)d_desc, &sl->work, codes, st,
+                                        g->mode, g->pool_min, g->quad_max, g->oct_max );
+  if( e != hipSuccess ) { fd_gpu_fail_q( "launch", e ); return NULL; }
+  return codes;
+}
+
+/* Finish: the codes to h_out where the DSM did not write them there, and
+   the slot's done event */
+static int fd_ring_finish( fd_ed25519_gpu_slot * sl, unsigned long n, int32_t const * codes, hipStream_t st ) {
+  hipError_t e = codes == sl->d_out ? hipMemcpyAsync( sl->h_out, sl->d_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st ) : hipSuccess;
+  if( e == hipSuccess ) e = hipEventRecord( sl->done, st );
+  return e == hipSuccess ? 0 : fd_gpu_fail( "D2H out, event", e );
+}
+
+/* A descriptor batch: copy-in, kernels, copy-out on the slot's stream */
 static int fd_slot_enqueue_( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n, void const * blob,
                              unsigned long blob_sz, void const * blob2, unsigned long blob2_sz,
                              fd_ed25519_gpu_desc_t const * desc, hipStream_t * used ) {
-  /* the batch's bytes are blob[0, blob_sz) followed by blob2[0, blob2_sz)
-     (a second piece: an in-place batch that continues past the caller's
-     ring wrap); descriptors index the concatenation */
-  unsigned long sz0 = blob_sz;
-  blob_sz += blob2_sz;
-  unsigned long doff = fd_desc_off( blob_sz );
-  /* a blob in a registered region is DMA'd from where it lies (no host
-     copy; descriptors go separately from the slot's pinned desc buffer);
-     anything else is staged into the slot's pinned buffer with the
-     descriptors packed after it (one copy) */
-  int direct = sl->h_blob != blob && sz0 && fd_registered( g, blob, sz0 )
-            && ( !blob2_sz || fd_registered( g, blob2, blob2_sz ) );
-  /* descriptors in a registered region too go from where they lie (a
-     verify tile building batches in its own registered buffers) */
-  int const ddirect = direct && fd_registered( g, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
-
-  /* ... and packed right after the blob in the device's layout: one copy */
-  int const packed = ddirect && !blob2_sz && (uint8_t const *)desc == (uint8_t const *)blob + doff
-                  && fd_registered( g, blob, doff + n * sizeof(fd_ed25519_gpu_desc_t) );
-  /* a registered span whose descriptors lie elsewhere (the feeder rebases
-     them; an in-place tile keeps them apart from the frags): the kernels
-     read them over PCIe from the slot's mapped descriptor buffer instead of
-     a second H2D copy per batch (closed loop +1-2.5 %, p50 -0.01 ms,
-     profiles/r06_zc_desc_ab_*.jsonl) */
-  int const zc = direct && !packed && sl->h_desc_dev;
-  if( direct ) {
-    if( !ddirect || zc ) memcpy( sl->h_desc, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
-  } else {
-    if( sl->h_blob != blob ) memcpy( sl->h_blob, blob, sz0 );
-    if( blob2_sz ) memcpy( sl->h_blob + sz0, blob2, blob2_sz );
-    memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
-    memcpy( sl->h_blob + doff, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
-  }
-  hipError_t e;
-  /* the slot's CU group only while another ring batch is in flight (a
-     lone batch runs faster spread over the whole device: depth-1 p50
-     0.755 ms there vs 0.80 ms on a third of the CUs) */
-  int busy = fd_ring_busy( g, sl );
-  int others = sl->mstream && n <= g->mask_max && (g->group_always || busy);
-  hipStream_t st = others ? sl->mstream : sl->stream;
-  *used = st;
-  if( packed ) {
-    if( (e = hipMemcpyAsync( sl->d_blob, blob, doff + n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess )
-      return fd_gpu_fail( "H2D blob+desc (registered)", e );
-  } else if( direct ) {
-    if( (e = hipMemcpyAsync( sl->d_blob, blob, sz0, hipMemcpyHostToDevice, st )) != hipSuccess )
-      return fd_gpu_fail( "H2D blob (registered)", e );
-    if( blob2_sz && (e = hipMemcpyAsync( sl->d_blob + sz0, blob2, blob2_sz, hipMemcpyHostToDevice, st )) != hipSuccess )
-      return fd_gpu_fail( "H2D blob piece 2 (registered)", e );
-    if( !zc && (e = hipMemcpyAsync( sl->d_blob + doff, ddirect ? (void const *)desc : (void const *)sl->h_desc,
-                             n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess )
-      return fd_gpu_fail( "H2D desc", e );
-  } else if( (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, doff + n * sizeof(fd_ed25519_gpu_desc_t), hipMemcpyHostToDevice, st )) != hipSuccess )
-    return fd_gpu_fail( "H2D blob+desc", e );
-  fd_ed25519_gpu_desc_t const * dd = zc ? sl->h_desc_dev : (fd_ed25519_gpu_desc_t const *)(sl->d_blob + doff);
-  /* up to out_direct_max signatures the DSM writes its codes into the
-     slot's pinned h_out itself: no D2H copy (a blit kernel and its gap,
-     ~5 us of every small batch's round trip); they are visible to the
-     host once the slot's done event completes */
-  int odirect = sl->h_out_dev && n <= g->out_direct_max;
-  sl->early = odirect && n <= g->early_max;
-  if( sl->early ) for( unsigned long i=0; i<n; i++ ) sl->h_out[i] = FD_CODE_PENDING;
-  if( (e = fd_ed25519_gpu_launch( n, sl->d_blob, blob_sz, dd, &sl->work, odirect ? sl->h_out_dev : sl->d_out, st,
-                                  g->mode, g->pool_min, g->quad_max, g->oct_max )) != hipSuccess )
-    return fd_gpu_fail( "launch", e );
-  if( !odirect && (e = hipMemcpyAsync( sl->h_out, sl->d_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, st )) != hipSuccess )
-    return fd_gpu_fail( "D2H out", e );
-  if( (e = hipEventRecord( sl->done, st )) != hipSuccess ) return fd_gpu_fail( "event", e );
+  fd_ring_src p = fd_ring_place( g, sl, blob, blob_sz, blob2, blob2_sz, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
+  hipStream_t st = *used = fd_ring_stream( g, sl, n );
+  void const * dd = fd_ring_h2d( sl, p, st );
+  int32_t * codes = dd ? fd_ring_verify( g, sl, n, blob_sz + blob2_sz, dd, st, 1 ) : NULL;
+  if( !codes || fd_ring_finish( sl, n, codes, st ) ) return FD_ED25519_ERR_GPU;
   sl->n = n; sl->n_txn = 0UL;
   return 0;
 }
 
-/* another ring batch still in flight? */
-static int fd_ring_busy( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot const * sl ) {
-  for( int s=0; s<g->depth; s++ )
-    if( &g->slot[s] != sl && g->slot[s].ticket && hipEventQuery( g->slot[s].done ) == hipErrorNotReady ) return 1;
-  return 0;
-}
-
-static void fd_slot_collect( fd_ed25519_gpu_slot * sl, int * out ) {
-  memcpy( out, sl->h_out, sl->n * sizeof(int) );
+/* a finished batch's results (res: a transaction batch's); NULL: not wanted */
+static void fd_slot_collect( fd_ed25519_gpu_slot * sl, int * codes, fd_ed25519_gpu_txn_result_t * res ) {
+  if( res ) memcpy( res, sl->h_res, sl->n_txn * sizeof(fd_ed25519_gpu_txn_result_t) );
+  if( codes && sl->n ) memcpy( codes, sl->h_out, sl->n * sizeof(int) );
 }
 
 extern "C" int fd_ed25519_gpu_verify_packed( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
@@ -1102,28 +1153,42 @@ extern "C" int fd_ed25519_gpu_verify_packed( fd_ed25519_gpu_t * g, unsigned long
   hipStream_t st = NULL;
   err = fd_slot_enqueue_( g, sl, n, blob, blob_sz, NULL, 0UL, desc, &st );
   if( (err = fd_slot_settle( g, sl, st, err )) ) return err;
-  fd_slot_collect( sl, out );
+  fd_slot_collect( sl, out, NULL );
   return 0;
 }
+
+/* Submit a ring batch of either kind: ensure() (what the kind needs
+   allocated: 0 or the error), a free slot, enqueue( sl, &st ), the ticket.
+   1 submitted, 0 the ring is full (poll first), < 0 an error. */
+template< class Ensure, class Enqueue >
+static int fd_ring_submit( fd_ed25519_gpu_t * g, void const * blob, unsigned long * ticket, Ensure ensure, Enqueue enqueue ) {
+  std::lock_guard<fd_ring_lock> guard( g->lock );
+  hipError_t e = hipSetDevice( g->device );
+  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
+  int err = ensure();
+  if( err ) return err;
+  fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
+  if( !sl ) return 0;
+  hipStream_t st = NULL;
+  err = enqueue( sl, &st );
+  if( err ) err = fd_slot_settle( g, sl, st, err );
+  sl->staged = 0;                        /* released, submitted or not (fd_ed25519_gpu_unstage) */
+  if( err ) return err;
+  *ticket = sl->ticket = g->next_ticket++;
+  return 1;
+}
+
+/* what the submits that do not wait for a slot return: a full ring is the caller's error */
+static inline int fd_submit_code( int r ) { return r == 1 ? 0 : r == 0 ? FD_ED25519_ERR_ARG : r; }
 
 extern "C" int fd_ed25519_gpu_try_submit2( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
                                            void const * blob2, unsigned long blob2_sz,
                                            fd_ed25519_gpu_desc_t const * desc, unsigned long * ticket ) {
   if( !g || !ticket || n > g->max_sigs || blob_sz > g->max_blob || blob2_sz > g->max_blob - blob_sz || (n && !desc)
       || (blob_sz && !blob) || (blob2_sz && !blob2) ) return FD_ED25519_ERR_ARG;
-  std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
-  if( !sl ) return 0;                    /* ring full: poll first */
-  hipStream_t st = NULL;
-  int err = fd_slot_enqueue_( g, sl, n, blob, blob_sz, blob2, blob2_sz, desc, &st );
-  if( err ) err = fd_slot_settle( g, sl, st, err );
-  sl->staged = 0;                        /* released, submitted or not (fd_ed25519_gpu_unstage) */
-  if( err ) return err;
-  sl->ticket = g->next_ticket++;
-  *ticket = sl->ticket;
-  return 1;
+  return fd_ring_submit( g, blob, ticket, []{ return 0; }, [&]( fd_ed25519_gpu_slot * sl, hipStream_t * st ) {
+    return fd_slot_enqueue_( g, sl, n, blob, blob_sz, blob2, blob2_sz, desc, st );
+  } );
 }
 
 extern "C" int fd_ed25519_gpu_try_submit( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
@@ -1133,8 +1198,7 @@ extern "C" int fd_ed25519_gpu_try_submit( fd_ed25519_gpu_t * g, unsigned long n,
 
 extern "C" int fd_ed25519_gpu_submit( fd_ed25519_gpu_t * g, unsigned long n, void const * blob, unsigned long blob_sz,
                                       fd_ed25519_gpu_desc_t const * desc, unsigned long * ticket ) {
-  int r = fd_ed25519_gpu_try_submit( g, n, blob, blob_sz, desc, ticket );
-  return r == 1 ? 0 : r == 0 ? FD_ED25519_ERR_ARG : r;
+  return fd_submit_code( fd_ed25519_gpu_try_submit( g, n, blob, blob_sz, desc, ticket ) );
 }
 
 /* A small direct-output batch's codes, each written once by the DSM into
@@ -1155,46 +1219,43 @@ static int fd_codes_query( void * p ) {
   return r == 1 ? 2 : r;
 }
 
-extern "C" int fd_ed25519_gpu_poll( fd_ed25519_gpu_t * g, unsigned long ticket, int * out, int block ) {
-  if( !g || !ticket ) return FD_ED25519_ERR_ARG;
-  fd_ed25519_gpu_slot * sl = NULL;
+/* Poll a ticket: res set wants a transaction ticket (codes optional), codes
+   alone a descriptor ticket -- the other kind's is refused and stays valid
+   -- and neither is a drain, which takes either kind.  1 collected, 0 in
+   flight (non-blocking), < 0 timed out or failed: the ticket stays valid. */
+static int fd_ring_poll( fd_ed25519_gpu_t * g, unsigned long ticket, int block, int * codes, fd_ed25519_gpu_txn_result_t * res ) {
+  fd_ed25519_gpu_slot * sl;
   {
     std::lock_guard<fd_ring_lock> guard( g->lock );
-    for( int s=0; s<g->depth && !sl; s++ ) if( g->slot[s].ticket == ticket ) sl = &g->slot[s];
-    /* a transaction ticket's results are fd_ed25519_gpu_poll_txns's; a
-       drain (out NULL) takes either kind.  The ticket stays valid */
-    if( sl && sl->n_txn && out ) return FD_ED25519_ERR_ARG;
+    sl = fd_slot_by_ticket( g, ticket );
+    if( !sl || ( (codes || res) && !res != !sl->n_txn ) ) return FD_ED25519_ERR_ARG;
   }
-  if( !sl ) return FD_ED25519_ERR_ARG;
-  if( (block & 1) && sl->early && out ) {   /* a drain (out NULL) waits for the event */
+  int landed = 0;   /* the codes are in ahead of the event: the slot comes back once that completes */
+  if( (block & 1) && sl->early && codes ) {   /* a drain waits for the event */
     fd_codes_ctx c = { sl, 1u };
-    int r = fd_wait_query( fd_codes_query, &c, FD_POLL_SPIN_NS, fd_timeout( g ) );
-    if( r < 0 ) return FD_ED25519_ERR_GPU;
-    if( r == 0 ) {
-      snprintf( fd_gpu_err, sizeof(fd_gpu_err), "wait: batch not complete after %ld ms", fd_timeout( g ) / 1000000L );
-      return FD_ED25519_ERR_GPU;        /* the ticket stays valid */
-    }
-    if( r == 1 ) {
-      /* the codes are in; the slot comes back once its event completes */
-      std::lock_guard<fd_ring_lock> guard( g->lock );
-      if( out ) fd_slot_collect( sl, out );
-      sl->early = 0; sl->retiring = 1;
-      if( block & FD_ED25519_GPU_POLL_KEEP ) sl->staged = 1;   /* its pinned buffers stay the caller's */
-      return 1;
-    }
+    int r = fd_batch_wait( fd_codes_query, &c, fd_timeout( g ), "" );
+    if( r < 0 ) return r;
+    landed = r == 1;
   } else if( block & 1 ) {
     int err = fd_event_wait( sl->done, fd_timeout( g ) );
-    if( err ) return err;               /* timed out or failed; the ticket stays valid */
+    if( err ) return err;
   } else {
     hipError_t e = hipEventQuery( sl->done );
     if( e == hipErrorNotReady ) return 0;
     if( e != hipSuccess ) return fd_gpu_fail( "poll", e );
   }
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  if( out ) fd_slot_collect( sl, out );
-  sl->ticket = 0; sl->early = 0; sl->n_txn = 0UL;
-  if( block & FD_ED25519_GPU_POLL_KEEP ) sl->staged = 1;   /* lent back to the caller (unstage to free) */
+  fd_slot_collect( sl, codes, res );
+  sl->early = 0;
+  if( landed ) sl->retiring = 1;
+  else { sl->ticket = 0; sl->n_txn = 0UL; }
+  if( block & FD_ED25519_GPU_POLL_KEEP ) sl->staged = 1;   /* its pinned buffers stay the caller's (unstage to free) */
   return 1;
+}
+
+extern "C" int fd_ed25519_gpu_poll( fd_ed25519_gpu_t * g, unsigned long ticket, int * out, int block ) {
+  if( !g || !ticket ) return FD_ED25519_ERR_ARG;
+  return fd_ring_poll( g, ticket, block, out, NULL );
 }
 
 /* Diagnostics: the device field products (fd_k_debug_fe, ops 0-6; op 7
@@ -1266,7 +1327,7 @@ extern "C" int fd_ed25519_gpu_debug_k( fd_ed25519_gpu_t * g, unsigned long n, vo
   if( err ) return err;
   hipError_t e;
   hipStream_t st = sl->stream;
-  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
+  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, NULL, 0UL, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
   uint64_t * d_k = (uint64_t *)g->dev_work[0].tab;   /* 1536 B of table scratch per signature >= 32 */
   uint8_t * h = (uint8_t *)malloc( 36UL * n );       /* k [4][n], status [n] */
   if( !h ) return FD_ED25519_ERR_GPU;
@@ -1360,7 +1421,7 @@ static int fd_diag_run( fd_ed25519_gpu_t * g, unsigned long n, void const * blob
   if( err ) return err;
   hipError_t e;
   hipStream_t st = sl->stream;
-  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
+  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, NULL, 0UL, desc, n * sizeof(fd_ed25519_gpu_desc_t) );
   fd_ed25519_gpu_desc_t const * d_desc = (fd_ed25519_gpu_desc_t const *)(sl->d_blob + doff);
   fd_ed25519_gpu_work_t const * w = &g->dev_work[0];
   /* device scratch: state words [n][8], k [4][n] (with_k), codes [n] (the
@@ -1586,8 +1647,7 @@ static void fd_long_pack( uint8_t * dst, fd_long_req const & r, unsigned long po
 /* the staged slot owning blob (the caller holds the stage) */
 static fd_ed25519_gpu_slot * fd_slot_of( fd_ed25519_gpu_t * g, void const * blob ) {
   std::lock_guard<fd_ring_lock> guard( g->lock );
-  for( int s=0; s<g->depth; s++ ) if( g->slot[s].h_blob == blob ) return &g->slot[s];
-  return NULL;
+  return fd_slot_by_blob( g, blob );
 }
 
 /* wait for the staged slot's queued work; on a timeout the slot is given
@@ -2031,7 +2091,7 @@ extern "C" int fd_ed25519_gpu_sign_packed( fd_ed25519_gpu_t * g, unsigned long n
   fd_ed25519_gpu_slot * sl;
   int err = fd_slot_take( g, blob, &sl );
   if( err ) return err;
-  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, sdesc, n * sizeof(fd_ed25519_gpu_sign_desc_t) );
+  unsigned long doff = fd_slot_stage( sl, blob, blob_sz, NULL, 0UL, sdesc, n * sizeof(fd_ed25519_gpu_sign_desc_t) );
   if( (err = fd_sgn_run( g, sl, n, doff + n * sizeof(fd_ed25519_gpu_sign_desc_t), blob_sz, blob_sz, doff, 1 )) ) return err;
   memcpy( sig_out, sl->h_sgn, 64UL*n );
   if( pub_out_opt ) memcpy( pub_out_opt, sl->h_sgn + 64UL*n, 32UL*n );
@@ -2206,10 +2266,13 @@ static int fd_txn_ensure( fd_ed25519_gpu_t * g, unsigned long n_txn, unsigned lo
 
 /* The ring slots' own transaction scratch (descriptors, results between
    the kernels, the pinned results the host reads): every slot that has
-   none yet gets it, so two batches in flight share nothing.  Caller holds
-   the ring lock and has set the device. */
-static int fd_txn_ring_ensure( fd_ed25519_gpu_t * g ) {
+   none yet gets it, so two batches in flight share nothing; timed: the
+   engine's four timing events too.  Caller holds the ring lock and has set
+   the device. */
+static int fd_txn_ring_ensure( fd_ed25519_gpu_t * g, int timed ) {
   hipError_t e;
+  for( int k=0; timed && k<4; k++ )
+    if( !g->txn_ring_ev[k] && (e = hipEventCreate( &g->txn_ring_ev[k] )) != hipSuccess ) { g->txn_ring_ev[k] = NULL; return fd_gpu_fail( "txn event", e ); }
   for( int s=0; s<g->depth; s++ ) {
     fd_ed25519_gpu_slot * sl = &g->slot[s];
     if( sl->t_desc && sl->t_res && sl->h_res_dev ) continue;
@@ -2233,7 +2296,7 @@ extern "C" int fd_ed25519_gpu_txns_reserve( fd_ed25519_gpu_t * g, unsigned long 
   /* the ring's slots too (dev_lock, then the ring lock, as
      fd_ed25519_gpu_verify_txns_packed orders them) */
   std::lock_guard<fd_ring_lock> rguard( g->lock );
-  return fd_txn_ring_ensure( g );
+  return fd_txn_ring_ensure( g, 0 );
 }
 
 static int fd_txn_args_ok( fd_ed25519_gpu_t const * g, unsigned long n_txn, void const * blob, unsigned long blob_sz, void const * txn,
@@ -2437,50 +2500,31 @@ extern "C" int fd_ed25519_gpu_debug_txn_descs( fd_ed25519_gpu_t * g, unsigned lo
 /* ------------------------------------------------------------------ */
 /* Transactions through the ring (fd_ed25519_gpu_submit_txns). */
 
-/* fd_slot_enqueue_ for a transaction batch: the blob reaches the slot's
-   device buffer as a descriptor batch's does (DMA from a registered
-   region, the slot's own staged h_blob as it lies, anything else staged),
-   and the batch's entries and claim prefix travel in the descriptors'
-   place: packed 16-aligned behind the staged blob in the one H2D copy, or,
-   beside a registered blob, in the slot's mapped descriptor buffer, which
-   the front kernel reads over the link (12 bytes per transaction).  Then
-   fd_k_txn_ring_front, the ring's verify launch on the slot's work area
-   with the slot's transaction descriptors, and fd_k_txn_ring_reduce, which
-   leaves the results in the slot's mapped pinned h_res.  ev: NULL, or four
-   events around the front kernel and the reduce. */
+/* A transaction batch: its tail, the entries and the claim prefix, is
+   built where fd_ring_place says (behind the staged blob, or beside a
+   registered one in the slot's mapped descriptor buffer).  Then
+   fd_k_txn_ring_front, the ring's verify launch with the slot's
+   transaction descriptors, and fd_k_txn_ring_reduce, which leaves the
+   results in the slot's mapped pinned h_res (final only then: no poll
+   takes the codes early).  ev: NULL, or four events around the front
+   kernel and the reduce. */
 static int fd_txn_slot_enqueue_( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl, unsigned long n_txn, void const * blob,
                                  unsigned long blob_sz, fd_ed25519_gpu_txn_t const * txn, hipStream_t * used, hipEvent_t const * ev ) {
-  unsigned long doff    = fd_desc_off( blob_sz );
-  unsigned long txn_sz  = n_txn * sizeof(fd_ed25519_gpu_txn_t);
-  unsigned long tail_sz = txn_sz + ( n_txn + 1UL ) * sizeof(uint32_t);   /* <= 16 n_txn <= the descriptors' room */
-  int direct = sl->h_blob != blob && blob_sz && fd_registered( g, blob, blob_sz );
-  int const zc = direct && sl->h_desc_dev;
-  uint8_t * tail = direct ? (uint8_t *)sl->h_desc : sl->h_blob + doff;
-  if( !direct ) {
-    if( sl->h_blob != blob && blob_sz ) memcpy( sl->h_blob, blob, blob_sz );
-    memset( sl->h_blob + blob_sz, 0, doff - blob_sz );
-  }
-  memcpy( tail, txn, txn_sz );
+  unsigned long txn_sz = n_txn * sizeof(fd_ed25519_gpu_txn_t);
+  /* <= 16 n_txn <= the descriptors' room */
+  fd_ring_src p = fd_ring_place( g, sl, blob, blob_sz, NULL, 0UL, NULL, txn_sz + ( n_txn + 1UL ) * sizeof(uint32_t) );
+  memcpy( p.tail, txn, txn_sz );
   /* the slot layout, read from the caller's bytes: a blob that was just
      staged is in the cache from the copy, one read in place from the pass
      fd_txn_try_submit made before it took the lock.  Should the bytes
      change between this and the DMA, the front kernel refuses whatever
      parses to another count than it claims here */
-  unsigned long n_sig = fd_ed25519_gpu_txn_claims( blob, blob_sz, txn, n_txn, (uint32_t *)( tail + txn_sz ) );
+  unsigned long n_sig = fd_ed25519_gpu_txn_claims( blob, blob_sz, txn, n_txn, (uint32_t *)( p.tail + txn_sz ) );
   if( n_sig > g->max_sigs ) return FD_ED25519_ERR_ARG;   /* nothing queued */
+  hipStream_t st = *used = fd_ring_stream( g, sl, n_sig );
   hipError_t e;
-  int busy = fd_ring_busy( g, sl );
-  int others = sl->mstream && n_sig <= g->mask_max && (g->group_always || busy);
-  hipStream_t st = others ? sl->mstream : sl->stream;
-  *used = st;
-  if( direct ) {
-    if( (e = hipMemcpyAsync( sl->d_blob, blob, blob_sz, hipMemcpyHostToDevice, st )) != hipSuccess )
-      return fd_gpu_fail( "H2D blob (registered)", e );
-    if( !zc && (e = hipMemcpyAsync( sl->d_blob + doff, sl->h_desc, tail_sz, hipMemcpyHostToDevice, st )) != hipSuccess )
-      return fd_gpu_fail( "H2D transactions", e );
-  } else if( (e = hipMemcpyAsync( sl->d_blob, sl->h_blob, doff + tail_sz, hipMemcpyHostToDevice, st )) != hipSuccess )
-    return fd_gpu_fail( "H2D blob+transactions", e );
-  uint8_t const * dt = zc ? (uint8_t const *)sl->h_desc_dev : sl->d_blob + doff;
+  uint8_t const * dt = (uint8_t const *)fd_ring_h2d( sl, p, st );
+  if( !dt ) return FD_ED25519_ERR_GPU;
   /* nothing to verify: the front kernel's results are final, straight to
      the pinned results */
   if( ev && (e = hipEventRecord( ev[0], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
@@ -2489,23 +2533,13 @@ static int fd_txn_slot_enqueue_( fd_ed25519_gpu_t * g, fd_ed25519_gpu_slot * sl,
                                                  st )) != hipSuccess )
     return fd_gpu_fail( "fd_ed25519_gpu_launch_txn_ring_front", e );
   if( ev && (e = hipEventRecord( ev[1], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
-  sl->early = 0;   /* the results are final only after the reduce */
-  if( n_sig ) {
-    int odirect = sl->h_out_dev && n_sig <= g->out_direct_max;
-    int32_t * codes = odirect ? sl->h_out_dev : sl->d_out;
-    if( (e = fd_ed25519_gpu_launch( n_sig, sl->d_blob, blob_sz, sl->t_desc, &sl->work, codes, st,
-                                    g->mode, g->pool_min, g->quad_max, g->oct_max )) != hipSuccess )
-      return fd_gpu_fail( "launch", e );
-    if( ev && (e = hipEventRecord( ev[2], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
-    if( (e = fd_ed25519_gpu_launch_txn_ring_reduce( n_txn, n_sig, sl->t_res, codes, sl->h_res_dev, st )) != hipSuccess )
-      return fd_gpu_fail( "fd_ed25519_gpu_launch_txn_ring_reduce", e );
-    if( ev && (e = hipEventRecord( ev[3], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
-    if( !odirect && (e = hipMemcpyAsync( sl->h_out, sl->d_out, n_sig * sizeof(int32_t), hipMemcpyDeviceToHost, st )) != hipSuccess )
-      return fd_gpu_fail( "D2H out", e );
-  } else if( ev ) {
-    if( (e = hipEventRecord( ev[2], st )) != hipSuccess || (e = hipEventRecord( ev[3], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
-  }
-  if( (e = hipEventRecord( sl->done, st )) != hipSuccess ) return fd_gpu_fail( "event", e );
+  int32_t * codes = fd_ring_verify( g, sl, n_sig, blob_sz, sl->t_desc, st, 0 );   /* n_sig 0: launches nothing */
+  if( !codes ) return FD_ED25519_ERR_GPU;
+  if( ev && (e = hipEventRecord( ev[2], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+  if( n_sig && (e = fd_ed25519_gpu_launch_txn_ring_reduce( n_txn, n_sig, sl->t_res, codes, sl->h_res_dev, st )) != hipSuccess )
+    return fd_gpu_fail( "fd_ed25519_gpu_launch_txn_ring_reduce", e );
+  if( ev && (e = hipEventRecord( ev[3], st )) != hipSuccess ) return fd_gpu_fail( "txn event", e );
+  if( fd_ring_finish( sl, n_sig, codes, st ) ) return FD_ED25519_ERR_GPU;
   sl->n = n_sig; sl->n_txn = n_txn;
   return 0;
 }
@@ -2524,8 +2558,7 @@ static int fd_txn_try_submit( fd_ed25519_gpu_t * g, unsigned long n_txn, void co
   int in_place = 0;
   if( blob_sz ) {
     std::lock_guard<fd_ring_lock> guard( g->lock );
-    in_place = fd_registered( g, blob, blob_sz );
-    for( int s=0; s<g->depth && !in_place; s++ ) in_place = g->slot[s].h_blob == blob;
+    in_place = fd_registered( g, blob, blob_sz ) || fd_slot_by_blob( g, blob );
   }
   if( in_place ) {
     unsigned long n_sig = 0UL;
@@ -2534,24 +2567,10 @@ static int fd_txn_try_submit( fd_ed25519_gpu_t * g, unsigned long n_txn, void co
       if( n_sig > g->max_sigs ) return FD_ED25519_ERR_ARG;
     }
   }
-  std::lock_guard<fd_ring_lock> guard( g->lock );
-  hipError_t e = hipSetDevice( g->device );
-  if( e != hipSuccess ) return fd_gpu_fail( "hipSetDevice", e );
-  int err = fd_txn_ring_ensure( g );   /* allocates only if fd_ed25519_gpu_txns_reserve has not */
-  if( err ) return err;
-  if( timed )
-    for( int k=0; k<4; k++ )
-      if( !g->txn_ring_ev[k] && (e = hipEventCreate( &g->txn_ring_ev[k] )) != hipSuccess ) { g->txn_ring_ev[k] = NULL; return fd_gpu_fail( "txn event", e ); }
-  fd_ed25519_gpu_slot * sl = fd_free_slot( g, blob );
-  if( !sl ) return 0;                    /* ring full: poll first */
-  hipStream_t st = NULL;
-  err = fd_txn_slot_enqueue_( g, sl, n_txn, blob, blob_sz, txn, &st, timed ? g->txn_ring_ev : NULL );
-  if( err ) err = fd_slot_settle( g, sl, st, err );
-  sl->staged = 0;                        /* released, submitted or not, as fd_ed25519_gpu_try_submit2 */
-  if( err ) return err;
-  sl->ticket = g->next_ticket++;
-  *ticket = sl->ticket;
-  return 1;
+  /* the scratch is allocated only if fd_ed25519_gpu_txns_reserve has not */
+  return fd_ring_submit( g, blob, ticket, [&]{ return fd_txn_ring_ensure( g, timed ); }, [&]( fd_ed25519_gpu_slot * sl, hipStream_t * st ) {
+    return fd_txn_slot_enqueue_( g, sl, n_txn, blob, blob_sz, txn, st, timed ? g->txn_ring_ev : NULL );
+  } );
 }
 
 extern "C" int fd_ed25519_gpu_try_submit_txns( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
@@ -2561,34 +2580,13 @@ extern "C" int fd_ed25519_gpu_try_submit_txns( fd_ed25519_gpu_t * g, unsigned lo
 
 extern "C" int fd_ed25519_gpu_submit_txns( fd_ed25519_gpu_t * g, unsigned long n_txn, void const * blob, unsigned long blob_sz,
                                            fd_ed25519_gpu_txn_t const * txn, unsigned long * ticket ) {
-  int r = fd_txn_try_submit( g, n_txn, blob, blob_sz, txn, ticket, 0 );
-  return r == 1 ? 0 : r == 0 ? FD_ED25519_ERR_ARG : r;
+  return fd_submit_code( fd_txn_try_submit( g, n_txn, blob, blob_sz, txn, ticket, 0 ) );
 }
 
 extern "C" int fd_ed25519_gpu_poll_txns( fd_ed25519_gpu_t * g, unsigned long ticket, fd_ed25519_gpu_txn_result_t * res, int * codes_opt,
                                          int block ) {
   if( !g || !ticket || !res ) return FD_ED25519_ERR_ARG;
-  fd_ed25519_gpu_slot * sl = NULL;
-  {
-    std::lock_guard<fd_ring_lock> guard( g->lock );
-    for( int s=0; s<g->depth && !sl; s++ ) if( g->slot[s].ticket == ticket ) sl = &g->slot[s];
-    if( sl && !sl->n_txn ) return FD_ED25519_ERR_ARG;   /* a descriptor ticket: fd_ed25519_gpu_poll's; it stays valid */
-  }
-  if( !sl ) return FD_ED25519_ERR_ARG;
-  if( block & 1 ) {
-    int err = fd_event_wait( sl->done, fd_timeout( g ) );
-    if( err ) return err;               /* timed out or failed; the ticket stays valid */
-  } else {
-    hipError_t e = hipEventQuery( sl->done );
-    if( e == hipErrorNotReady ) return 0;
-    if( e != hipSuccess ) return fd_gpu_fail( "poll", e );
-  }
-  std::lock_guard<fd_ring_lock> guard( g->lock );
-  memcpy( res, sl->h_res, sl->n_txn * sizeof(fd_ed25519_gpu_txn_result_t) );
-  if( codes_opt && sl->n ) memcpy( codes_opt, sl->h_out, sl->n * sizeof(int) );
-  sl->ticket = 0; sl->early = 0; sl->n_txn = 0UL;
-  if( block & FD_ED25519_GPU_POLL_KEEP ) sl->staged = 1;   /* lent back to the caller (unstage to free) */
-  return 1;
+  return fd_ring_poll( g, ticket, block, codes_opt, res );
 }
 
 extern "C" unsigned long fd_ed25519_gpu_txn_ring_allocs( fd_ed25519_gpu_t * g ) {
@@ -2601,8 +2599,8 @@ extern "C" int fd_ed25519_gpu_txn_ring_timed( fd_ed25519_gpu_t * g, unsigned lon
                                               fd_ed25519_gpu_txn_t const * txn, fd_ed25519_gpu_txn_result_t * res, float * kernel_ms ) {
   if( !kernel_ms || !res ) return FD_ED25519_ERR_ARG;
   unsigned long ticket = 0UL;
-  int r = fd_txn_try_submit( g, n_txn, blob, blob_sz, txn, &ticket, 1 );
-  if( r != 1 ) return r == 0 ? FD_ED25519_ERR_ARG : r;
+  int r = fd_submit_code( fd_txn_try_submit( g, n_txn, blob, blob_sz, txn, &ticket, 1 ) );
+  if( r ) return r;
   if( (r = fd_ed25519_gpu_poll_txns( g, ticket, res, NULL, 1 )) != 1 ) {
     if( r < 0 ) fd_abandon_ticket( g, ticket );
     return r < 0 ? r : FD_ED25519_ERR_GPU;
